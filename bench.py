@@ -1,7 +1,16 @@
 """Benchmark: GAT-HiC training steps/sec on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N --steps K --warmup W] [--workload synth-20000|synth-2000]
-                  [--dist-mode slab|allgather] [--simulate-world P]
+                  [--dist-mode slab|allgather] [--simulate-world P] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, the configuration, ``final_loss``).
+``--dump-outputs DIR`` also writes what the last timed step returned (``loss``,
+``coords``) and the parameters it left (``params``) as ``DIR/<name>.npy``; the workload and the
+weights are seeded, so two builds run with the same arguments can be compared output for output.
+``--full`` adds everything that takes runs of its own after the timed steps: ``reference_loop``,
+the eager per-kernel pass (``kernels``, ``roofline``, ``gemm``, ``collectives``) and the CPU oracle
+(``cpu_baseline``, ``parity``); a plain run reports those blocks as null / empty.
 
 One step = zero_grad + GATConv (MFMA lin_l + fused logits, edge-softmax aggregation) + MLP tail
 + fused distance/MSE loss + backward + Adam, over the whole synthetic Hi-C graph, inputs resident
@@ -26,8 +35,8 @@ process (before any GPU call) and exits with its code; it exits non-zero if fewe
 visible.
 
 Rank 0 prints ONE JSON line.  ``value`` = K / (max over ranks of the barrier-bracketed wall time of
-the K timed steps).  Per-kernel times (``kernels``, ``roofline.avg_launch_ms``) come from HIP
-events around every launch in an EAGER pass of K steps run right after the timed region (a graph
+the K timed steps).  With ``--full``: per-kernel times (``kernels``, ``roofline.avg_launch_ms``) come from
+HIP events around every launch in an EAGER pass of K steps run right after the timed region (a graph
 replay hides kernel boundaries); rocprofv3's per-kernel averages of the same command are committed
 under profiles/ to cross-check them.  ``roofline.frac`` = HBM bytes the dominant kernel really
 moves (PMC FETCH_SIZE x 2 + WRITE_SIZE, rocprofv3 --pmc passes recorded in profiles/*pmc_traffic*,
@@ -301,6 +310,23 @@ def parity_block(dev, cpu):
                     "mm-formula cdist (the reference's arithmetic, SURVEY fact 8)"}
 
 
+def dump_outputs(path, out, model):
+    """``--dump-outputs``: what the caller of the timed step received from its last call -- ``loss``
+    (float64 scalar) and ``coords`` ([N, 3] float32) -- and ``params``, the flat float32 parameters
+    that step's Adam update left (the order of ``model.flat_parameters()``), one ``<name>.npy`` each
+    (a few MB in all).  The step's ``stats`` are left out: the fields a loss kind does not fill are
+    NaN by contract (include/hicgat.h), which an element-wise comparison of two dumps would trip on."""
+    loss, _, coords = out
+    arrays = {"loss": loss.detach().double().cpu().numpy(),
+              "coords": coords.detach().float().cpu().numpy(),
+              "params": torch.cat([p.detach().reshape(-1) for p in model.flat_parameters()]).float().cpu().numpy()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step written to {path}: "
+        + ", ".join(f"{k}{list(v.shape)} {v.dtype}" for k, v in arrays.items()))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -441,7 +467,14 @@ def main():
     ap.add_argument("--no-bare", action="store_true",
                     help="--simulate-world: skip the second timing of each rank without the collectives")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the reference's "
+                         "loop control, the eager per-kernel pass (kernels, roofline, gemm, collectives) and the CPU "
+                         "oracle (cpu_baseline, parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, coords) and the parameters it "
+                         "left behind as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU oracle out")
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--cpu-warmup", type=int, default=2)
     ap.add_argument("--eager", action="store_true",
@@ -451,6 +484,10 @@ def main():
     ap.add_argument("--selftest-cpu", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     args.graph = not args.eager and not args.selftest_cpu
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.simulate_world:
+        ap.error("--dump-outputs writes the outputs of a real step; --simulate-world has none")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -553,50 +590,56 @@ def main():
     if timed_events:
         evs[0].record()
     for k in range(args.steps):
-        loss = step()[0]
+        last = step()
         if timed_events:
             evs[k + 1].record()
     sync()
     t1 = time.perf_counter()
+    loss = last[0]
     if world > 1 or args.selftest_cpu:
         torch.distributed.barrier()
     step_ms = [evs[k].elapsed_time(evs[k + 1]) for k in range(args.steps)] if timed_events else []
-    # the reference's loop control (HiC-GNN_main.py:123-132, hicgat.train.train): the same steps, each
-    # followed by the host read of the loss and the lossdiff test -- one device -> host sync per step,
-    # so the next step's launch waits for it (timed like the headline, reported beside it)
-    sync()
-    if world > 1 or args.selftest_cpu:
-        torch.distributed.barrier()
-    old, diffs = 1.0, []
-    r0 = time.perf_counter()
-    for k in range(args.steps):
-        lv = float(step()[0].item())
-        diffs.append(abs(old - lv))
-        old = lv
-    sync()
-    loop_s = time.perf_counter() - r0
-    if world > 1 or args.selftest_cpu:
-        torch.distributed.barrier()
-        t = torch.tensor([loop_s], dtype=torch.float64, device=dev if dev.type == "cuda" else "cpu")
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        loop_s = float(t.item())
-    ref_loop = {"value": args.steps / loop_s, "unit": "steps/s", "ms_per_step": 1e3 * loop_s / args.steps,
-                "steps": args.steps, "last_lossdiff": diffs[-1],
-                "note": "the HiC-GNN_main.py:128 loop: each step's loss read on the host and |old - loss| > thresh "
-                        "tested before the next step is launched (graph replay + one D2H sync per step); the "
-                        "headline value replays the steps back to back"}
-    # per-kernel HIP events: an eager pass of the same length right after the timed region
-    kernels.TIMERS = {} if timed_events else None
+    if args.dump_outputs and rank == 0:
+        # the step's outputs are persistent buffers that a later step overwrites: written out now
+        dump_outputs(args.dump_outputs, last, model)
     sharded = world > 1 or args.selftest_cpu
-    if sharded:
-        hdist.COMM_TIMERS = {}      # and every collective of the same eager pass, on its stream
-    if timed_events or sharded:
-        for k in range(args.steps):
-            eager_step()
+    ref_loop = None
+    if args.full:
+        # the reference's loop control (HiC-GNN_main.py:123-132, hicgat.train.train): the same steps, each
+        # followed by the host read of the loss and the lossdiff test -- one device -> host sync per step,
+        # so the next step's launch waits for it (timed like the headline, reported beside it)
         sync()
+        if sharded:
+            torch.distributed.barrier()
+        old, diffs = 1.0, []
+        r0 = time.perf_counter()
+        for k in range(args.steps):
+            lv = float(step()[0].item())
+            diffs.append(abs(old - lv))
+            old = lv
+        sync()
+        loop_s = time.perf_counter() - r0
+        if sharded:
+            torch.distributed.barrier()
+            t = torch.tensor([loop_s], dtype=torch.float64, device=dev if dev.type == "cuda" else "cpu")
+            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            loop_s = float(t.item())
+        ref_loop = {"value": args.steps / loop_s, "unit": "steps/s", "ms_per_step": 1e3 * loop_s / args.steps,
+                    "steps": args.steps, "last_lossdiff": diffs[-1],
+                    "note": "the HiC-GNN_main.py:128 loop: each step's loss read on the host and |old - loss| > thresh "
+                            "tested before the next step is launched (graph replay + one D2H sync per step); the "
+                            "headline value replays the steps back to back"}
+        # per-kernel HIP events: an eager pass of the same length right after the timed region
+        kernels.TIMERS = {} if timed_events else None
+        if sharded:
+            hdist.COMM_TIMERS = {}      # and every collective of the same eager pass, on its stream
+        if timed_events or sharded:
+            for k in range(args.steps):
+                eager_step()
+            sync()
     timers, kernels.TIMERS = kernels.TIMERS or {}, None
     comm = None
-    if sharded:
+    if sharded and args.full:
         meas = hdist.comm_report()
         hdist.COMM_TIMERS = None
         # the communicator's own rank count: an all-reduce of a one per rank
@@ -701,9 +744,12 @@ def main():
         "final_loss": loss_v,
         "reference_loop": ref_loop,
         "roofline": roof,
-        "gemm": gemm_block(args.workload, kern_t) if not args.selftest_cpu else None,
+        "gemm": gemm_block(args.workload, kern_t) if args.full and not args.selftest_cpu else None,
         "kernels": kern_t,
+        "full": bool(args.full),
     }
+    if args.dump_outputs:
+        result["dump_outputs"] = args.dump_outputs
     if comm is not None:
         result["collectives"] = comm
     if sharded:
@@ -711,7 +757,7 @@ def main():
                            "nnz_per_rank": [int(v) for v in runner.plan.nnz]}
     if graph_error is not None:
         result["graph_error"] = graph_error
-    if rank == 0 and world == 1 and not args.selftest_cpu and not args.no_cpu_baseline \
+    if args.full and rank == 0 and world == 1 and not args.selftest_cpu and not args.no_cpu_baseline \
             and args.model == "GATNetSelectiveResidualsUpdated":
         log("[bench] cpu baseline (oracle) ...")
         cb = cpu_baseline(wl, args.seed, steps=args.cpu_steps, warmup=args.cpu_warmup)

@@ -23,7 +23,8 @@ def _run(*args, timeout=300):
 
 
 def test_bench_gpus2_self_launches_two_ranks():
-    rc, res, err = _run("--gpus", "2", "--selftest-cpu", "--steps", "2", "--warmup", "1")
+    # --full: the eager pass that times every collective belongs to the full run
+    rc, res, err = _run("--gpus", "2", "--selftest-cpu", "--steps", "2", "--warmup", "1", "--full")
     assert rc == 0, err[-3000:]
     assert res["n_gpus"] == 2 and res["steps"] == 2
     assert res["config"]["parallelism"].startswith("dst-row shard x2")
