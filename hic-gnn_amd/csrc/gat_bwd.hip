@@ -378,6 +378,20 @@ int agg_bwd_src_split_launch(const int *rowptr_s, const int *col_s, int row_begi
   return HICGAT_OK;
 }
 
+// gat_generic.hip: the supported-shape rule and the kernels of every supported shape but (2, 256)
+// (launched without kSrcOccLds: unmeasured for those shapes)
+bool gat_shape_supported(int H, int C);
+int agg_bwd_rows_generic_launch(int H, int C, int row_begin, int row_end, int act, const float *g, const float *y,
+                                const float *bias, const float *out2, float *dout, int64_t ldq4,
+                                float *row_stats, hipStream_t s);
+int agg_bwd_dst_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
+                               const float *h, const float *a_src, const float *a_dst, const float *dout, float ns,
+                               float *row_stats, hipStream_t s);
+int agg_bwd_src_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
+                               const float *h, const float *a_src, const float *a_dst, const float *row_stats,
+                               int64_t ldr, const float *dout, int64_t ldq4, const float *att_s, const float *att_d,
+                               float ns, float *dh, float *da_src, bool remap, hipStream_t s);
+
 }  // namespace hicgat
 
 using namespace hicgat;
@@ -387,9 +401,12 @@ extern "C" int hicgat_gat_agg_bwd_dst(const int32_t *rowptr, const int32_t *col,
                                       const float *a_src, const float *a_dst, const float *dout,
                                       float neg_slope, float *row_stats, hicgat_stream_t stream) {
   if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
   if (row_end == row_begin) return HICGAT_OK;
   if (!rowptr || !col || !h || !a_src || !a_dst || !dout || !row_stats) return HICGAT_EINVAL;
+  if (H != 2 || C != 256)
+    return agg_bwd_dst_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, dout, neg_slope,
+                                      row_stats, (hipStream_t)stream);
   const int rows = row_end - row_begin;
   hipLaunchKernelGGL(agg_bwd_dst_h2c256_kernel, dim3((rows + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, rowptr, col, row_begin, row_end, h, a_src, a_dst, dout,
@@ -406,12 +423,16 @@ extern "C" int hicgat_gat_agg_bwd_src_ld(const int32_t *rowptr, const int32_t *c
                                          float neg_slope, float *dh, float *da_src,
                                          hicgat_stream_t stream) {
   if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
   if (ld_stats < 4 * H || ld_stats % 4 || ld_dout < H * C || ld_dout % 4) return HICGAT_EINVAL;
   if (row_end == row_begin) return HICGAT_OK;
   if (!rowptr || !col || !h || !a_src || !a_dst || !row_stats || !dout || !att_src || !att_dst ||
       !dh || !da_src)
     return HICGAT_EINVAL;
+  if (H != 2 || C != 256)
+    return agg_bwd_src_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats,
+                                      dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, true,
+                                      (hipStream_t)stream);
   const int rows = row_end - row_begin;
   hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<false>), dim3((rows + 3) / 4), dim3(256), kSrcOccLds,
                      (hipStream_t)stream, rowptr, col, row_begin, row_end, h, a_src, a_dst,
@@ -432,12 +453,16 @@ extern "C" int hicgat_gat_agg_bwd_src_ex(const int32_t *rowptr, const int32_t *c
                                      dout, ld_dout, att_src, att_dst, neg_slope, dh, da_src, stream);
   if (flags & ~HICGAT_SRC_ROUND_ROBIN) return HICGAT_EINVAL;
   if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
   if (ld_stats < 4 * H || ld_stats % 4 || ld_dout < H * C || ld_dout % 4) return HICGAT_EINVAL;
   if (row_end == row_begin) return HICGAT_OK;
   if (!rowptr || !col || !h || !a_src || !a_dst || !row_stats || !dout || !att_src || !att_dst ||
       !dh || !da_src)
     return HICGAT_EINVAL;
+  if (H != 2 || C != 256)
+    return agg_bwd_src_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats,
+                                      dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, false,
+                                      (hipStream_t)stream);
   const int rows = row_end - row_begin;
   hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<false, false>), dim3((rows + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, rowptr, col, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
@@ -465,9 +490,12 @@ extern "C" int hicgat_gat_agg_bwd_rows(int N, int H, int C, int row_begin, int r
   if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
   if (act && (ld_dout < (int64_t)H * C || ld_dout % 4)) return HICGAT_EINVAL;
   if (act != 0 && act != 1) return HICGAT_EINVAL;
-  if (H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
   if (row_end == row_begin) return HICGAT_OK;
   if (!g || !y || !bias || !out2 || !row_stats || (act && !dout)) return HICGAT_EINVAL;
+  if (H != 2 || C != 256)
+    return agg_bwd_rows_generic_launch(H, C, row_begin, row_end, act, g, y, bias, out2, dout, ld_dout / 4, row_stats,
+                                       (hipStream_t)stream);
   const int rows = row_end - row_begin;
   if (act)
     hipLaunchKernelGGL(agg_bwd_rows_kernel<1>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,

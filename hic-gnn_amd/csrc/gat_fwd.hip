@@ -178,6 +178,12 @@ int agg_fwd_split_launch(const int *rowptr, const int *col, const int *rowptr_s,
   return HICGAT_OK;
 }
 
+// gat_generic.hip: the supported-shape rule and the kernels of every supported shape but (2, 256)
+bool gat_shape_supported(int H, int C);
+int agg_fwd_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
+                           const float *h, const float *a_src, const float *a_dst, const float *bias, float ns,
+                           int act, float *out, float *out2, float *row_stats, hipStream_t s);
+
 }  // namespace hicgat
 
 using namespace hicgat;
@@ -207,9 +213,12 @@ extern "C" int hicgat_gat_agg_fwd_act(const int32_t *rowptr, const int32_t *col,
                                       float *row_stats, hicgat_stream_t stream) {
   if (N < 0 || nnz < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
   if (act != 0 && act != 1) return HICGAT_EINVAL;
-  if (H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
   if (row_end == row_begin) return HICGAT_OK;
   if (!rowptr || !col || !h || !a_src || !a_dst || !bias || !out || !row_stats) return HICGAT_EINVAL;
+  if (H != 2 || C != 256)   // the generic kernels, without the (2, 256) launch's occupancy cap (unmeasured there)
+    return agg_fwd_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out,
+                                  out2, row_stats, (hipStream_t)stream);
   const int rows = row_end - row_begin;
   const dim3 grid((rows + 3) / 4), block(256);
   hipStream_t s = (hipStream_t)stream;

@@ -5,6 +5,8 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
   hicgat.nn.SAGEConv                          ~ layers.SAGEConv (layers.py:12-79)
   hicgat.gat_models.GATNetSelectiveResidualsUpdated / GATNetHeadsChanged3LayersLeakyReLUv2 / Net
                                               ~ models.py:614-691 / :1010-1047 / :14-55
+  hicgat.gat_models.GATNetHeadsChangedLeakyReLU / GATNetReduced (eval only)
+                                              ~ models.py:181-222 / :1414-1459
   hicgat.graph.load_input / cont2dist / convert_to_matrix / Adj
                                               ~ utils.py:10-80 (+ torch_sparse.SparseTensor)
   hicgat.train.train / main                   ~ HiC-GNN_main.py:107-160
@@ -16,6 +18,7 @@ Compute runs in libhicgat.so (include/hicgat.h); there is no CPU fallback.
 """
 from . import _lib, align, dist, embed, graph, graphs, io, kernels, kr, metrics, nn, ops, optim, synth, train  # noqa: F401
 from .gat_models import (GATNetHeadsChanged3LayersLeakyReLUv2,  # noqa: F401
+                         GATNetHeadsChangedLeakyReLU, GATNetReduced,
                          GATNetSelectiveResidualsUpdated, MODELS, Net)
 from .graph import Adj, Data, Truth, cont2dist, convert_to_matrix, load_input  # noqa: F401
 from .nn import GATConv, SAGEConv  # noqa: F401

@@ -375,6 +375,13 @@ class SimComm:
 
 class ShardedTrainer:
     def __init__(self, model, x, adj, truth, lr=1e-3, kind="mse", group=None, kern=None, mode="auto", comm=None):
+        conv = getattr(model, "conv", None)
+        shape = tuple(getattr(conv, a, None) for a in ("in_channels", "out_channels", "heads"))
+        if shape != (512, 256, 2):
+            # before any collective: the sharded kernels (gat_xagg.hip, the packed all-gather rows) are
+            # written for this one layer
+            raise NotImplementedError(f"ShardedTrainer runs models whose conv is GATConv(512, 256, heads=2); "
+                                      f"{type(model).__name__}.conv has (in, out, heads) = {shape}")
         if kern is None:
             from .kernels import default
             kern = default()

@@ -3,6 +3,9 @@
 * ``GATNetSelectiveResidualsUpdated``       -- models.py:614-691 (flagship, 601 475 parameters).
 * ``GATNetHeadsChanged3LayersLeakyReLUv2``  -- models.py:1010-1047 (411 651 parameters).
 * ``Net``                                   -- models.py:14-55, the SAGEConv baseline (697 475).
+* ``GATNetHeadsChangedLeakyReLU``           -- models.py:181-222, GATConv(512, 128, heads=2) (175 171).
+* ``GATNetReduced``                         -- models.py:1414-1459, GATConv(512, 512, heads=2), the model
+                                               evaluate.py:86 loads (806 403); inference only.
 
 Submodules are registered in the reference's order (so the same seed gives the same initial
 weights and the same state_dict keys).  ``forward`` returns the N x N distance matrix like the
@@ -11,7 +14,7 @@ fused path used by the training loop (distance + MSE [+ Pearson] without materia
 """
 import torch
 import torch.nn.functional as F
-from torch.nn import LayerNorm, Linear
+from torch.nn import Dropout, LayerNorm, LeakyReLU, Linear
 
 from . import ops
 from .nn import GATConv, SAGEConv
@@ -106,6 +109,75 @@ class GATNetHeadsChanged3LayersLeakyReLUv2(_CoordsModel):
         return self.tail(self.conv(x, edge_index))
 
 
+class GATNetHeadsChangedLeakyReLU(_CoordsModel):
+    """models.py:181-222: GATConv(512, 128, heads=2) -> 256-128-64-32-3 with leaky_relu(0.01) between."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 128, heads=2, concat=True)
+        self.densea = Linear(256, 128)
+        self.dense1 = Linear(128, 64)
+        self.dense2 = Linear(64, 32)
+        self.dense3 = Linear(32, 3)
+        self.leaky_relu = LeakyReLU()
+
+    conv_act = None     # leaky_relu(0.01) stays a torch op on the GATConv output
+
+    def tail(self, x):
+        x = F.leaky_relu(x)
+        x = F.leaky_relu(_lin(self.densea, x))
+        x = F.leaky_relu(_lin(self.dense1, x))
+        x = F.leaky_relu(_lin(self.dense2, x))
+        return _lin(self.dense3, x)
+
+    post_act = tail
+
+    def get_model(self, x, edge_index):
+        return self.tail(self.conv(x, edge_index))
+
+
+class GATNetReduced(_CoordsModel):
+    """models.py:1414-1459: GATConv(512, 512, heads=2) -> relu -> 1024-256-64-3 with relu between.
+    The reference's training ``forward`` applies Dropout(0.4) after the GATConv and after densea
+    (``get_model`` does not); feature dropout is not implemented here, so in training mode ``forward``
+    and ``loss`` refuse instead of training without it.  Eval mode and ``get_model`` run."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 512, heads=2, concat=True)
+        self.densea = Linear(1024, 256)
+        self.dense1 = Linear(256, 64)
+        self.dense2 = Linear(64, 3)
+        self.dropout = Dropout(p=0.4)
+
+    conv_act = "relu"   # the relu after the GATConv runs in the aggregation's epilogue
+
+    def post_act(self, x):
+        x = F.relu(_lin(self.densea, x))
+        x = F.relu(_lin(self.dense1, x))
+        return _lin(self.dense2, x)
+
+    def tail(self, x):
+        return self.post_act(F.relu(x))
+
+    def get_model(self, x, edge_index):
+        return self.post_act(self.conv(x, edge_index, act=self.conv_act))
+
+    def _no_training(self):
+        if self.training:
+            raise NotImplementedError("GATNetReduced trains with Dropout(0.4) in the reference (models.py:1432, "
+                                      ":1438); feature dropout is not implemented, so the model runs in eval "
+                                      "mode only (model.eval())")
+
+    def forward(self, x, edge_index):
+        self._no_training()
+        return super().forward(x, edge_index)
+
+    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None):
+        self._no_training()
+        return super().loss(x, edge_index, truth, kind, tile_range, stats)
+
+
 class Net(_CoordsModel):
     """models.py:14-55: SAGEConv(512, 512) -> relu -> 512-256-128-64-3 with relu between."""
 
@@ -129,4 +201,6 @@ MODELS = {
     "GATNetSelectiveResidualsUpdated": GATNetSelectiveResidualsUpdated,
     "GATNetHeadsChanged3LayersLeakyReLUv2": GATNetHeadsChanged3LayersLeakyReLUv2,
     "Net": Net,
+    "GATNetHeadsChangedLeakyReLU": GATNetHeadsChangedLeakyReLU,
+    "GATNetReduced": GATNetReduced,
 }

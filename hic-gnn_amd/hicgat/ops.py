@@ -312,7 +312,8 @@ class _GATConvFn(torch.autograd.Function):
         ctx.rows_state = None
         if train:
             ctx.save_for_backward(x, W, al, ar, h, a_src, a_dst, row_stats, rowptr, col, out, out2, b)
-            if FUSE_ROWS:
+            if FUSE_ROWS and (H, D // H) == (2, 256):
+                # (only this shape: the fused epilogue writes (2, 256)-layout row stats)
                 # the one-kernel tail that consumes ``out`` may run this layer's rows pass in its
                 # backward's epilogue (_FusedTailFn; hicgat_tail_bwd_fused_rows): it finds these
                 # operands on ``out`` and records the dout it wrote in the shared state
@@ -892,12 +893,27 @@ def prepacked(model, job):
         model._hicgat_prepack = None
 
 
+GAT_SHAPE_RULE = "out_channels % 128 == 0, heads * out_channels a multiple of 256 and <= 1024, heads <= 4"
+
+
+def gat_shape_supported(H, C):
+    """Whether the aggregation kernels run GATConv(heads=H, out_channels=C) (include/hicgat.h; the
+    rule of gat_generic.hip, usable without the library loaded)."""
+    H, C = int(H), int(C)
+    return 1 <= H <= 4 and C > 0 and C % 128 == 0 and (H * C) % 256 == 0 and H * C <= 1024
+
+
 def gat_conv(x, W, att_l, att_r, bias, adj, negative_slope=0.2, act=None):
     """GATConv forward; ``act="relu"`` returns relu(GATConv(x)) with the relu fused."""
+    H, C = att_l.shape[-2], att_l.shape[-1]
+    if not gat_shape_supported(H, C):
+        raise NotImplementedError(f"GATConv(heads={H}, out_channels={C}) is not supported by the aggregation "
+                                  f"kernels: they need {GAT_SHAPE_RULE}")
     if adj.rowptr32 is None or adj.rowptr32.device != x.device:
         adj.to(x.device)
-    return _GATConvFn.apply(x, W, att_l, att_r, bias, adj.rowptr32, adj.col32, negative_slope, _ACTS[act],
-                            adj.tiles())
+    # the matrix-core tiled form (gat_tiles.hip) is (2, 256) only: every other shape gathers
+    tiles = adj.tiles() if (H, C) == (2, 256) else None
+    return _GATConvFn.apply(x, W, att_l, att_r, bias, adj.rowptr32, adj.col32, negative_slope, _ACTS[act], tiles)
 
 
 class _PairDistFn(torch.autograd.Function):

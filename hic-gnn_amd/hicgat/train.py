@@ -103,14 +103,8 @@ def parse_conversions(text):
     raise ValueError("Invalid conversion input.")
 
 
-def main(argv=None):
-    """HiC-GNN_main.py's pipeline: list -> convert_to_matrix -> zero diagonal -> KRnorm ->
-    embeddings -> load_input -> one model per conversion value -> best dSCC -> weights / PDB / log.
-
-    As in the reference (HiC-GNN_main.py:108-132), EVERY conversion value trains a fresh model
-    against ``cont2dist(y, 0.5)`` and is scored against that same truth: the value only labels the
-    run (the reference never passes it to cont2dist); the models differ by their random init (one
-    seed for the whole sweep, the RNG stream continuing from model to model)."""
+def make_parser():
+    """The CLI's argument parser (HiC-GNN_main.py's flags)."""
     p = argparse.ArgumentParser(description="Train a GAT-HiC model on the MI355X path "
                                             "(HiC-GNN_main.py flags).")
     p.add_argument("matrix", help="Hi-C list (bin_i bin_j count) or dense matrix text file")
@@ -127,6 +121,18 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", default=None, help="prefix for <out>_weights.pt / _structure.pdb / _log.txt")
     p.add_argument("--no-kr", action="store_true", help="the input is already KR-normalised (skip KRnorm)")
+    return p
+
+
+def main(argv=None):
+    """HiC-GNN_main.py's pipeline: list -> convert_to_matrix -> zero diagonal -> KRnorm ->
+    embeddings -> load_input -> one model per conversion value -> best dSCC -> weights / PDB / log.
+
+    As in the reference (HiC-GNN_main.py:108-132), EVERY conversion value trains a fresh model
+    against ``cont2dist(y, 0.5)`` and is scored against that same truth: the value only labels the
+    run (the reference never passes it to cont2dist); the models differ by their random init (one
+    seed for the whole sweep, the RNG stream continuing from model to model)."""
+    p = make_parser()
     a = p.parse_args(argv)
     conv = parse_conversions(a.conversions)
     mat = np.loadtxt(a.matrix)

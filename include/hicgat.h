@@ -81,8 +81,13 @@ int hicgat_gat_att_logits(const float *h, const float *att_src, const float *att
  * every per-row array is indexed by the GLOBAL row id: h, a_src, a_dst [N, .] (the neighbour
  * rows of the shard must be present), out [N, H*C] (rows of the range written),
  * row_stats [N, 4H] = (max[H], sum[H], delta[H], da_dst[H]) -- max/sum written here, delta/da_dst
- * by hicgat_gat_agg_bwd_dst.  Supported: H == 2, C == 256 (the GATConv(512, 256, heads=2) of
- * models.py:619); other shapes return HICGAT_EUNSUPPORTED. */
+ * by hicgat_gat_agg_bwd_dst.  Supported: C % 128 == 0, H*C a multiple of 256, H*C <= 1024, H <= 4
+ * (every GATConv of models.py: (H, C) = (1, 256), (1, 512), (2, 128), (2, 256), (2, 512), (4, 256), ...);
+ * other shapes return HICGAT_EUNSUPPORTED.  H == 2, C == 256 (the flagship's GATConv(512, 256,
+ * heads=2), models.py:619) has kernels of its own; the rest share the generic ones (gat_generic.hip).
+ * The same set holds for hicgat_gat_agg_fwd_act, hicgat_gat_agg_bwd_dst, hicgat_gat_agg_bwd_rows and
+ * hicgat_gat_agg_bwd_src / _ld / _ex; the tiled (hicgat_gat_agg_*_tiled) and aggregate-first
+ * (hicgat_xagg_*) forms stay H == 2, C == 256. */
 int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
                        int row_begin, int row_end, const float *h, const float *a_src,
                        const float *a_dst, const float *bias, float neg_slope, float *out,
@@ -91,7 +96,8 @@ int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz
  * follows the GATConv at models.py:637), act = 0 the plain sum + bias.  out2 != NULL (training)
  * also writes, from the same gathered rows, out2 [N, H*C] = sum_j alpha_ij lrelu'(e_ij) h_j and
  * S3[i,h] = sum_j alpha_ij lrelu'(e_ij) into row_stats[i, 2H..3H) -- the inputs that let
- * hicgat_gat_agg_bwd_rows form the destination half of the backward without a gather. */
+ * hicgat_gat_agg_bwd_rows form the destination half of the backward without a gather.
+ * Supported shapes: as hicgat_gat_agg_fwd. */
 int hicgat_gat_agg_fwd_act(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
                            int row_begin, int row_end, const float *h, const float *a_src,
                            const float *a_dst, const float *bias, float neg_slope, int act,
@@ -105,7 +111,8 @@ int hicgat_gat_agg_fwd_act(const int32_t *rowptr, const int32_t *col, int N, int
  *   has r as a neighbour; needs dout, row_stats of all those i):
  *   dh[r] = sum_i alpha_ir dout[i] + da_src[r] (x) att_l + da_dst[r] (x) att_r,
  *   da_src[r,h] = sum_i alpha_ir lrelu'(e_ir) (g_ir - delta[i,h]).
- * Requires a structurally symmetric CSR (utils.py:71 to_symmetric guarantees it). */
+ * Requires a structurally symmetric CSR (utils.py:71 to_symmetric guarantees it).
+ * Supported shapes: as hicgat_gat_agg_fwd (every pass; ld_stats >= 4H and a multiple of 4). */
 int hicgat_gat_agg_bwd_dst(const int32_t *rowptr, const int32_t *col, int N, int H, int C,
                            int row_begin, int row_end, const float *h, const float *a_src,
                            const float *a_dst, const float *dout, float neg_slope,

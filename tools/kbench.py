@@ -1,9 +1,11 @@
 """Per-kernel timing on the synth-20000 workload (HIP events, interleaved rounds).
 
-  python tools/kbench.py [--libs a.so,b.so] [--reps 20] [--workload synth-20000]
+  python tools/kbench.py [--libs a.so,b.so] [--reps 20] [--workload synth-20000] [--heads H --channels C]
 
 Loads each library build (same C ABI) in turn via ctypes, runs every kernel of the training step
-on identical inputs and prints avg/min ms and algorithmic GB/s (bench.agg_bytes) per kernel."""
+on identical inputs and prints avg/min ms and algorithmic GB/s (bench.agg_bytes) per kernel.
+--heads / --channels other than 2 / 256: a GATConv(512, C, heads=H) layer instead of the flagship's, and
+only the GAT jobs that exist for it (linear_att, the aggregation passes, param_grad)."""
 import argparse
 import ctypes
 import os
@@ -23,6 +25,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--workload", default="synth-20000")
     ap.add_argument("--only", default="", help="comma-separated job-name substrings to run")
+    ap.add_argument("--heads", type=int, default=2)
+    ap.add_argument("--channels", type=int, default=256)
     a = ap.parse_args()
     import bench
     import hicgat
@@ -33,12 +37,16 @@ def main():
     nnz = adj.device_nnz
     torch.manual_seed(0)
     model = hicgat.GATNetSelectiveResidualsUpdated().to(dev)
-    conv = model.conv
+    H, C = a.heads, a.channels
+    flagship = (H, C) == (2, 256)
+    if not hicgat.ops.gat_shape_supported(H, C):
+        raise SystemExit(f"unsupported GATConv shape: heads {H}, channels {C} ({hicgat.ops.GAT_SHAPE_RULE})")
+    conv = model.conv if flagship else hicgat.GATConv(512, C, heads=H).to(dev)
     W, al, ar, b = conv.lin_l.weight.detach(), conv.att_l.detach(), conv.att_r.detach(), conv.bias.detach()
     K0 = kernels.HipKernels()
     h, a_s, a_d = K0.linear_att(x, W, al, ar)
     out = torch.empty_like(h)
-    rs = torch.zeros(n, 8, device=dev)
+    rs = torch.zeros(n, 4 * H, device=dev)
     out2 = torch.empty_like(h)
     K0.agg_fwd_act(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, b, 0.2, 1, out, out2, rs)
     dout = torch.randn_like(h) * 1e-3
@@ -86,7 +94,7 @@ def main():
         "gat_agg_bwd_rows": lambda K: K.agg_bwd_rows(0, n, 1, dout, out, b, out2, dh, rs),
         "gat_agg_bwd_src": lambda K: K.agg_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, al, ar,
                                                    0.2, dh, da),
-        "param_grad": lambda K: K.param_grad(h, dout, da, rs, 2),
+        "param_grad": lambda K: K.param_grad(h, dout, da, rs, H),
         "pairdist_mse_fused": lambda K: K.fused_loss(coords, truth.buf, n, 0, 0, -1, stats, loss, dc),
         "pairdist_combined": lambda K: K.fused_loss(coords, truth.buf, n, 1, 0, -1, stats, loss, dc),
         "pairdist_support": lambda K: K.fused_loss_support(coords, truth.support, n, 0, stats, loss, dc),
@@ -105,6 +113,10 @@ def main():
         "torch_dw_512x512": lambda K: dh.t().mm(x),   # the library GEMM (hipBLASLt) on the same shape
         "torch_fwd_densea": lambda K: torch.nn.functional.linear(out, Wa, ba),
     }
+    if not flagship:
+        keep = ("gat_linear_att", "gat_agg_fwd", "gat_agg_fwd_train", "gat_agg_bwd_dst", "gat_agg_bwd_rows",
+                "gat_agg_bwd_src", "param_grad")
+        jobs = {k: v for k, v in jobs.items() if k in keep}
     if a.only:
         keys = [k.strip() for k in a.only.split(",") if k.strip()]
         jobs = {k: v for k, v in jobs.items() if any(x in k for x in keys)}
@@ -128,8 +140,10 @@ def main():
         if base in ("gat_agg_fwd", "gat_agg_fwd_train", "gat_agg_bwd_dst", "gat_agg_bwd_rows", "gat_agg_bwd_src",
                     "pairdist_mse_fused", "pairdist_combined"):
             kb = {"pairdist_combined": "pairdist_mse_fused", "gat_agg_fwd_train": "gat_agg_fwd"}.get(base, base)
-            alg = f"{bench.agg_bytes(kb, n, nnz) / (min(ts) * 1e-3) / 1e9:9.0f} GB/s alg"
-        print(f"{lname:28s} {jname:22s} med {np.median(ts):8.4f} ms  min {min(ts):8.4f} ms  {alg}", flush=True)
+            bts = bench.agg_bytes(kb, n, nnz, d=H * C, h=H) if kb.startswith("gat_") else bench.agg_bytes(kb, n, nnz)
+            alg = f"{bts / (min(ts) * 1e-3) / 1e9:9.0f} GB/s alg"
+        tag = jname if flagship else f"{jname}@h{H}c{C}"
+        print(f"{lname:28s} {tag:22s} med {np.median(ts):8.4f} ms  min {min(ts):8.4f} ms  {alg}", flush=True)
 
 
 if __name__ == "__main__":
