@@ -76,10 +76,14 @@ __device__ __forceinline__ double shfl_xor_d(double v, int m) {
 }
 
 // Row partials of the background form: each thread's 8-column partial of every row it touches goes
-// to LDS (stride kRowPad float4: 16 lanes of a row-sum read hit distinct banks) and threads 128..255
-// add the 16 per row in tx order at the end, while 0..127 add the column partials -- instead of
-// three 16-lane DPP sums per row inside the pair loop (~20 % of its VALU issue).
-constexpr int kRowPad = 17;
+// to LDS and threads 128..255 add the 16 per row in tx order at the end, while 0..127 add the column
+// partials -- instead of three 16-lane DPP sums per row inside the pair loop (~20 % of its VALU
+// issue).  Three planes (x, y, z) of [128 rows][kRowPad] floats, 30 KB where float4 entries took 34:
+// with the planar colred the workgroup holds 39.4 KB of LDS, four per CU.  kRowPad = 20: a 32-lane
+// half's ds_write_b32 (two ty, rows 4 apart = 80 dwords = 16 banks) is conflict-free, and the row
+// sums read their 16 floats as four conflict-free ds_read_b128 (80-B rows: 16 lanes, 16 slots).
+constexpr int kRowPad = 20;
+constexpr int kRowPlane = BT * kRowPad;
 
 // Per-thread accumulators of one tile: the moments and the column partials of its 8 columns.
 struct TileAcc {
@@ -95,14 +99,18 @@ template <int MODE, bool VEC, int KIND, bool MASK, int K0, int K1, bool BG = fal
 __device__ __forceinline__ void tile_rows(const float *__restrict__ T, int64_t ldt, int64_t row0, int64_t col0,
                                           int N, int I, int J, float bg,
                                           const float *tile, const float (*sc)[BT][3], int tx, int ty,
-                                          const float *cx, const float *cy, const float *cz, const int *gj,
-                                          float4 *__restrict__ prow, TileAcc &A, float4 *rowpart) {
+                                          const float *cx, const float *cy, const float *cz, int gj0,
+                                          float4 *__restrict__ prow, TileAcc &A, float *rowpart) {
   constexpr bool PEARSON = KIND == KIND_COMBINED, ABSL = KIND == KIND_CONTRASTIVE;
 #pragma unroll 1
   for (int k = K0; k < K1; ++k) {
     const int lr = ty * 4 + (k & 3) + (k >> 2) * 64;
     const int gi = I * BT + lr;
     const float rx = sc[0][lr][0], ry = sc[0][lr][1], rz = sc[0][lr][2];
+    // the thread's global columns from one base (gj0 + 0..3, gj0 + 64..67): one register, not eight
+    int gj[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) gj[q] = gj0 + (q & 3) + (q >> 2) * 64;
     float tv[8];
     if (BG) {   // background form: every pair at the background value, the support added later
 #pragma unroll
@@ -172,7 +180,9 @@ __device__ __forceinline__ void tile_rows(const float *__restrict__ T, int64_t l
       A.az[q] = fmaf(-w, dz, A.az[q]);
     }
     if constexpr (RLDS) {   // the thread's 8-column partial of row lr; the 16 of a row are added at the end
-      rowpart[lr * kRowPad + tx] = make_float4(px, py, pz, 0.f);
+      rowpart[lr * kRowPad + tx] = px;
+      rowpart[kRowPlane + lr * kRowPad + tx] = py;
+      rowpart[2 * kRowPlane + lr * kRowPad + tx] = pz;
     } else {
       px = sum16(px);
       py = sum16(py);
@@ -190,7 +200,7 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 template <int KIND, int K0, int K1, bool BG = false, bool RLDS = false>
 __device__ __forceinline__ void tile_rows_pk(const float *tile, float bg, const float (*sc)[BT][3], int tx, int ty,
                                              const float *cx, const float *cy, const float *cz,
-                                             float4 *__restrict__ prow, TileAcc &A, float4 *rowpart) {
+                                             float4 *__restrict__ prow, TileAcc &A, float *rowpart) {
   constexpr bool PEARSON = KIND == KIND_COMBINED, ABSL = KIND == KIND_CONTRASTIVE;
   f2 cx2[4], cy2[4], cz2[4], ax2[4], ay2[4], az2[4];
 #pragma unroll
@@ -252,7 +262,9 @@ __device__ __forceinline__ void tile_rows_pk(const float *tile, float bg, const 
       az2[h] = __builtin_elementwise_fma(-w, dz, az2[h]);
     }
     if constexpr (RLDS) {
-      rowpart[lr * kRowPad + tx] = make_float4(px.x + px.y, py.x + py.y, pz.x + pz.y, 0.f);
+      rowpart[lr * kRowPad + tx] = px.x + px.y;
+      rowpart[kRowPlane + lr * kRowPad + tx] = py.x + py.y;
+      rowpart[2 * kRowPlane + lr * kRowPad + tx] = pz.x + pz.y;
     } else {
       const float sx = sum16(px.x + px.y), sy = sum16(py.x + py.y), sz = sum16(pz.x + pz.y);
       if (tx == 0) prow[lr] = make_float4(sx, sy, sz, 0.f);
@@ -314,8 +326,11 @@ struct SupportArgs {
   int64_t ntiles = 0;
 };
 
+// The background form is latency-bound and is built for four workgroups per CU: <= 128 VGPRs (the
+// launch bound makes the compiler hold to them) and <= 40 KB of LDS; tests/test_pairdist_resources_host.py
+// checks both from the kernel metadata.
 template <int MODE, bool VEC, int KIND, bool BG = false, bool SUP = false>
-__global__ __launch_bounds__(256, 1) void pairdist_tile_kernel(const float *__restrict__ coords,
+__global__ __launch_bounds__(256, BG ? 4 : 1) void pairdist_tile_kernel(const float *__restrict__ coords,
                                                             const float *__restrict__ T, int N,
                                                             int64_t ldt, int64_t row0, int64_t col0,
                                                             int nb, int64_t t0,
@@ -334,11 +349,11 @@ __global__ __launch_bounds__(256, 1) void pairdist_tile_kernel(const float *__re
   // one dynamic LDS array: [T tile 128x128 fp32 (VEC only)] -- 64 KiB, 16-B aligned
   extern __shared__ __attribute__((aligned(16))) float tile[];
   __shared__ float sc[2][BT][3];
-  __shared__ float4 colred[4][BT];
+  __shared__ float colred[3][4][BT];   // planar x / y / z: [wave][column]
   __shared__ double mred[4][7];
   constexpr bool RL = BG;
-  __shared__ float4 rowpart_s[RL ? BT * kRowPad : 1];
-  float4 *rowpart = RL ? rowpart_s : nullptr;
+  __shared__ __attribute__((aligned(16))) float rowpart_s[RL ? 3 * kRowPlane : 1];
+  float *rowpart = RL ? rowpart_s : nullptr;
   const int64_t t = t0 + blockIdx.x;
   int I, J;
   if (MODE == MODE_SYM) {
@@ -385,12 +400,11 @@ __global__ __launch_bounds__(256, 1) void pairdist_tile_kernel(const float *__re
   __builtin_amdgcn_s_barrier();
 
   float cx[8], cy[8], cz[8];
-  int gj[8];
+  const int gj0 = J * BT + tx * 4;
   TileAcc A;
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int lc = tx * 4 + (q & 3) + (q >> 2) * 64;
-    gj[q] = J * BT + lc;
     cx[q] = sc[1][lc][0];
     cy[q] = sc[1][lc][1];
     cz[q] = sc[1][lc][2];
@@ -400,18 +414,31 @@ __global__ __launch_bounds__(256, 1) void pairdist_tile_kernel(const float *__re
   const bool interior = I != J && (I + 1) * BT <= N && (J + 1) * BT <= N;   // block-uniform
   if (VEC) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // this wave's first 16 rows landed
   constexpr bool PK = (VEC || BG) && MODE == MODE_SYM;   // packed interior path (tile_rows_pk)
-  if (interior) {
-    if constexpr (PK) tile_rows_pk<KIND, 0, 4, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
-    else tile_rows<MODE, VEC, KIND, false, 0, 4>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj, prow, A, rowpart);
+  if constexpr (BG) {
+    // no T image to wait for between the halves: one branch around both, so the interior and the
+    // masked form never share a live range (the two half-calls stay: each half's moments are
+    // summed on their own and then added, the order the records have always had)
+    if (interior) {
+      tile_rows_pk<KIND, 0, 4, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
+      tile_rows_pk<KIND, 4, 8, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
+    } else {
+      tile_rows<MODE, VEC, KIND, true, 0, 4, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+      tile_rows<MODE, VEC, KIND, true, 4, 8, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    }
   } else {
-    tile_rows<MODE, VEC, KIND, true, 0, 4, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj, prow, A, rowpart);
-  }
-  if (VEC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // and the second 16
-  if (interior) {
-    if constexpr (PK) tile_rows_pk<KIND, 4, 8, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
-    else tile_rows<MODE, VEC, KIND, false, 4, 8>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj, prow, A, rowpart);
-  } else {
-    tile_rows<MODE, VEC, KIND, true, 4, 8, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj, prow, A, rowpart);
+    if (interior) {
+      if constexpr (PK) tile_rows_pk<KIND, 0, 4, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
+      else tile_rows<MODE, VEC, KIND, false, 0, 4>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    } else {
+      tile_rows<MODE, VEC, KIND, true, 0, 4, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    }
+    if (VEC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // and the second 16
+    if (interior) {
+      if constexpr (PK) tile_rows_pk<KIND, 4, 8, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
+      else tile_rows<MODE, VEC, KIND, false, 4, 8>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    } else {
+      tile_rows<MODE, VEC, KIND, true, 4, 8, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    }
   }
 
   // column partials: reduce over the 4 ty of this wave (lanes l, l^16, l^32, l^48), then waves
@@ -423,8 +450,12 @@ __global__ __launch_bounds__(256, 1) void pairdist_tile_kernel(const float *__re
   }
   if (lane < 16) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q)
-      colred[wv][tx * 4 + (q & 3) + (q >> 2) * 64] = make_float4(A.ax[q], A.ay[q], A.az[q], 0.f);
+    for (int q = 0; q < 8; ++q) {
+      const int lc = tx * 4 + (q & 3) + (q >> 2) * 64;
+      colred[0][wv][lc] = A.ax[q];
+      colred[1][wv][lc] = A.ay[q];
+      colred[2][wv][lc] = A.az[q];
+    }
   }
   if (MODE == MODE_SYM) {
     constexpr bool PEARSON = KIND == KIND_COMBINED;
@@ -441,26 +472,30 @@ __global__ __launch_bounds__(256, 1) void pairdist_tile_kernel(const float *__re
   }
   __syncthreads();
   if (tid < BT) {
-    float4 s = colred[0][tid];
+    float s[3];
 #pragma unroll
-    for (int w2 = 1; w2 < 4; ++w2) {
-      const float4 o = colred[w2][tid];
-      s.x += o.x;
-      s.y += o.y;
-      s.z += o.z;
+    for (int c = 0; c < 3; ++c) {
+      s[c] = colred[c][0][tid];
+#pragma unroll
+      for (int w2 = 1; w2 < 4; ++w2) s[c] += colred[c][w2][tid];
     }
-    prow[BT + tid] = s;
+    prow[BT + tid] = make_float4(s[0], s[1], s[2], 0.f);
   } else if (RL) {
     const int lr = tid - BT;
-    float4 s = rowpart[lr * kRowPad];
+    float s[3];
 #pragma unroll
-    for (int q = 1; q < 16; ++q) {
-      const float4 o = rowpart[lr * kRowPad + q];
-      s.x += o.x;
-      s.y += o.y;
-      s.z += o.z;
+    for (int c = 0; c < 3; ++c) {
+      float v[16];
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const float4 o = *reinterpret_cast<const float4 *>(&rowpart[c * kRowPlane + lr * kRowPad + 4 * q4]);
+        v[4 * q4] = o.x; v[4 * q4 + 1] = o.y; v[4 * q4 + 2] = o.z; v[4 * q4 + 3] = o.w;
+      }
+      s[c] = v[0];
+#pragma unroll
+      for (int q = 1; q < 16; ++q) s[c] += v[q];   // tx order, as the 16 entries were always added
     }
-    prow[lr] = make_float4(s.x, s.y, s.z, 0.f);
+    prow[lr] = make_float4(s[0], s[1], s[2], 0.f);
   }
   if (MODE == MODE_SYM && tid < 7) {
     mom[(size_t)t * 8 + tid] = ((mred[0][tid] + mred[1][tid]) + mred[2][tid]) + mred[3][tid];
