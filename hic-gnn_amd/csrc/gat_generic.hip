@@ -1,199 +1,28 @@
-// The GATConv aggregation kernels of gat_fwd.hip / gat_bwd.hip for every supported (H, C) other than
-// (2, 256): the shapes the reference's model zoo instantiates (models.py: GATConv(512, 128, heads=2),
-// (512, 512, heads=2), (256, 256, heads=4), (512, 512, heads=1), ...).  Supported set:
-//   C % 128 == 0,  D = H*C a multiple of 256,  D <= 1024,  H <= 4.
-// (2, 256) keeps its own kernels (agg_*_h2c256_kernel) with their measured launch parameters.
-//
-// Same design: one wave per destination row, four rows per 256-thread workgroup, no [nnz, H, C]
-// tensor, no float atomics, fixed summation order; neighbour index and alphas broadcast with
-// readlane from the lane that owns the edge; each gather one scalar base + per-lane dwordx4.
-//
-// Lane / head mapping.  A lane holds V = D/256 float4 slices of a row; slice v is float4
-// #(64v + lane), columns 256v + 4*lane ...  A half wave's 128 columns of a slice lie inside one head
-// (C % 128 == 0): lanes 0-31 of slice v belong to head (256v)/C, lanes 32-63 to head (256v + 128)/C.
-// Where the two are the same head (every slice when C % 256 == 0) the alpha of a neighbour is one
-// scalar broadcast as in the (2, 256) kernel; where they differ (every slice when C == 128, the
-// middle slice of C == 384) the lane selects between two broadcast alphas by lane >> 5, and the
-// per-head dot products of the backward are sums over a half wave (formed here as whole-wave sums of
-// values that the other half contributes 0 to).
+// The GATConv aggregation kernels for every supported (H, C) other than (2, 256): the shapes the
+// reference's model zoo instantiates (models.py: GATConv(512, 128, heads=2), (512, 512, heads=2),
+// (256, 256, heads=4), (512, 512, heads=1), ...).  The per-row bodies are gat_agg.hpp's, shared with
+// the (2, 256) entry kernels of gat_fwd.hip / gat_bwd.hip; here are the __global__ wrappers that pick
+// the row, and their launches.
 //
 // Launched without the dynamic-LDS occupancy caps of the (2, 256) launches (kAggFwdOccLds,
 // kSrcOccLds): those were measured for (2, 256) at N = 20000 only, nobody has measured them for
 // these shapes.
-#include "common.hpp"
+#include "gat_agg.hpp"
 
 namespace hicgat {
 
-namespace {
-
-template <int H, int C> struct Shape {
-  static_assert(C % 128 == 0 && (H * C) % 256 == 0 && H * C <= 1024 && H >= 1 && H <= 4, "unsupported GAT shape");
-  static constexpr int D = H * C, V = D / 256, Q = D / 4;
-  static constexpr int HP = H <= 1 ? 1 : H <= 2 ? 2 : 4;        // heads padded to a power of two
-  static constexpr int TR = 2 * HP;                             // transpose_reduce width for 2H values
-  __host__ __device__ static constexpr int lo(int v) { return (256 * v) / C; }
-  __host__ __device__ static constexpr int hi(int v) { return (256 * v + 128) / C; }
-  // neighbours gathered per inner step: V float4 loads per lane each.  The forward keeps 16 (V <= 2)
-  // or 12-16 (V >= 3) loads in flight, the source pass 4-8: at D = 1024 the TRAIN forward carries 32
-  // accumulator floats, and U = 8 there (128 gathered floats) does not fit 128 VGPRs.
-  static constexpr int UFwd = V <= 2 ? 8 : 4;
-  static constexpr int USrc = V <= 2 ? 4 : 2;
-  static constexpr int UDst = 2;
-};
-
-// this lane's value among per-head values a[] for its slice v (upper: lane >> 5)
-template <int H, int C> __device__ __forceinline__ float pick(const float (&a)[H], int v, bool upper) {
-  using S = Shape<H, C>;
-  return S::lo(v) == S::hi(v) ? a[S::lo(v)] : (upper ? a[S::hi(v)] : a[S::lo(v)]);
-}
-// the same of lane l's a[] (broadcast through SGPRs; one readlane where the slice lies in one head)
-template <int H, int C> __device__ __forceinline__ float bcast_pick(const float (&a)[H], int l, int v, bool upper) {
-  using S = Shape<H, C>;
-  const float x = readlane_f(a[S::lo(v)], l);
-  if (S::lo(v) == S::hi(v)) return x;
-  const float y = readlane_f(a[S::hi(v)], l);
-  return upper ? y : x;
-}
-// add x (a partial sum over this lane's slice v) to its head's entry of a[]
-template <int H, int C, int NA> __device__ __forceinline__ void scatter_add(float (&a)[NA], int stride, int off,
-                                                                         int v, bool upper, float x) {
-  using S = Shape<H, C>;
-  if (S::lo(v) == S::hi(v)) {
-    a[S::lo(v) * stride + off] += x;
-  } else {
-    a[S::lo(v) * stride + off] += upper ? 0.f : x;
-    a[S::hi(v) * stride + off] += upper ? x : 0.f;
-  }
-}
-
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) {
-  return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
-}
-
-}  // namespace
-
-// ---- forward: softmax statistics, then the gather (gat_fwd.hip agg_fwd_h2c256_kernel) -----------
 template <int H, int C, bool TRAIN, int ACT>
 __global__ __launch_bounds__(256) void agg_fwd_generic_kernel(
     const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
     const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
     const float *__restrict__ bias, float ns, float *__restrict__ out, float *__restrict__ out2,
     float *__restrict__ row_stats) {
-  using S = Shape<H, C>;
-  constexpr int U = S::UFwd, V = S::V, Q = S::Q;
-  const int lane = lane_id();
-  const bool upper = lane >= 32;
   const int i = row_begin + xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_in_block();
   if (i >= row_end) return;
-  const int beg = rowptr[i], end = rowptr[i + 1];
-  float ad[H], m[H], s[H];
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) {
-    ad[hh] = a_dst[(size_t)i * H + hh];
-    m[hh] = -INFINITY;
-    s[hh] = 0.f;
-  }
-  for (int e = beg + lane; e < end; e += 64) {
-    const float *as = a_src + (size_t)col[e] * H;
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) m[hh] = fmaxf(m[hh], lrelu(as[hh] + ad[hh], ns));
-  }
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) m[hh] = wave_max(m[hh]);
-  for (int e = beg + lane; e < end; e += 64) {
-    const float *as = a_src + (size_t)col[e] * H;
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) s[hh] += expf(lrelu(as[hh] + ad[hh], ns) - m[hh]);
-  }
-  float den[H];
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) {
-    s[hh] = wave_sum(s[hh]);
-    den[hh] = s[hh] + 1e-16f;
-  }
-
-  const float4 *h4 = reinterpret_cast<const float4 *>(h);
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 acc[V], acs[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) acc[v] = acs[v] = z4;
-  float t[H];
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) t[hh] = 0.f;
-  for (int base = beg; base < end; base += 64) {
-    const int e = base + lane;
-    int j = i;  // padded slots gather the (valid) own row with weight 0
-    float p[H], q[H];
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) p[hh] = q[hh] = 0.f;
-    if (e < end) {
-      j = col[e];
-      const float *as = a_src + (size_t)j * H;
-#pragma unroll
-      for (int hh = 0; hh < H; ++hh) {
-        const float ee = as[hh] + ad[hh];
-        p[hh] = expf(lrelu(ee, ns) - m[hh]) / den[hh];
-        if (TRAIN) {
-          q[hh] = p[hh] * (ee > 0.f ? 1.f : ns);
-          t[hh] += q[hh];
-        }
-      }
-    }
-    const int cnt = min(64, end - base);
-    for (int k = 0; k < cnt; k += U) {
-      float4 g[U][V];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const size_t jj = (size_t)readlane_i(j, k + u);
-#pragma unroll
-        for (int v = 0; v < V; ++v) g[u][v] = h4[jj * Q + 64 * v + lane];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          acc[v] = f4_fma(bcast_pick<H, C>(p, k + u, v, upper), g[u][v], acc[v]);
-          if (TRAIN) acs[v] = f4_fma(bcast_pick<H, C>(q, k + u, v, upper), g[u][v], acs[v]);
-        }
-      }
-    }
-  }
-  const float4 *b4 = reinterpret_cast<const float4 *>(bias);
-  float4 *o4 = reinterpret_cast<float4 *>(out) + (size_t)i * Q + lane;
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    float4 r = f4_add(acc[v], b4[64 * v + lane]);
-    if (ACT == 1) r = f4_relu(r);
-    o4[64 * v] = r;
-  }
-  float *rs = row_stats + (size_t)i * 4 * H;
-  if (TRAIN) {
-    float4 *q4 = reinterpret_cast<float4 *>(out2) + (size_t)i * Q + lane;
-#pragma unroll
-    for (int v = 0; v < V; ++v) q4[64 * v] = acs[v];
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) t[hh] = wave_sum(t[hh]);
-    if (lane == 0) {
-#pragma unroll
-      for (int hh = 0; hh < H; ++hh) {
-        rs[2 * H + hh] = t[hh];   // S3, parked in the delta slot until agg_bwd_rows replaces it
-        rs[3 * H + hh] = 0.f;
-      }
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) {
-      rs[hh] = m[hh];
-      rs[H + hh] = s[hh];
-    }
-  }
+  agg_fwd_row<H, C, TRAIN, ACT, false>(i, rowptr, col, nullptr, nullptr, h, a_src, a_dst, bias, ns, out, out2,
+                                       row_stats);
 }
 
-// ---- destination side without a gather (gat_bwd.hip agg_bwd_rows_kernel) -------------------------
 template <int H, int C, int ACT>
 __global__ __launch_bounds__(256) void agg_bwd_rows_generic_kernel(int row_begin, int row_end,
                                                                    const float *__restrict__ g,
@@ -202,152 +31,21 @@ __global__ __launch_bounds__(256) void agg_bwd_rows_generic_kernel(int row_begin
                                                                    const float *__restrict__ out2,
                                                                    float *__restrict__ dout, int64_t ldq,
                                                                    float *__restrict__ row_stats) {
-  using S = Shape<H, C>;
-  constexpr int V = S::V, Q = S::Q, TR = S::TR, HP = S::HP;
-  const int lane = lane_id();
-  const bool upper = lane >= 32;
   const int i = row_begin + blockIdx.x * 4 + wave_in_block();
   if (i >= row_end) return;
-  const float4 *g4 = reinterpret_cast<const float4 *>(g) + (size_t)i * Q + lane;
-  const float4 *y4 = reinterpret_cast<const float4 *>(y) + (size_t)i * Q + lane;
-  const float4 *q4 = reinterpret_cast<const float4 *>(out2) + (size_t)i * Q + lane;
-  const float4 *b4 = reinterpret_cast<const float4 *>(bias) + lane;
-  float val[TR];   // [hh]: <dout, y - bias> of head hh, [HP + hh]: <dout, out2>
-#pragma unroll
-  for (int k = 0; k < TR; ++k) val[k] = 0.f;
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    float4 d = g4[64 * v];
-    const float4 yv = y4[64 * v], qv = q4[64 * v], bv = b4[64 * v];
-    if (ACT == 1) {
-      d = make_float4(yv.x <= 0.f ? 0.f : d.x, yv.y <= 0.f ? 0.f : d.y, yv.z <= 0.f ? 0.f : d.z,
-                      yv.w <= 0.f ? 0.f : d.w);
-      reinterpret_cast<float4 *>(dout)[(size_t)i * ldq + 64 * v + lane] = d;   // ldq: row stride, float4
-    }
-    scatter_add<H, C>(val, 1, 0, v, upper, f4_dot(d, f4_sub(yv, bv)));
-    scatter_add<H, C>(val, 1, HP, v, upper, f4_dot(d, qv));
-  }
-  transpose_reduce<TR>(val, lane);   // value k (summed over the wave) in lane k * 64 / TR
-  float dl[H], pq[H];
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) {
-    dl[hh] = readlane_f(val[0], hh * (64 / TR));
-    pq[hh] = readlane_f(val[0], (HP + hh) * (64 / TR));
-  }
-  if (lane == 0) {
-    float *rs = row_stats + (size_t)i * 4 * H;
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) {
-      const float s3 = rs[2 * H + hh];   // from the forward
-      rs[2 * H + hh] = dl[hh];
-      rs[3 * H + hh] = fmaf(-dl[hh], s3, pq[hh]);
-    }
-  }
+  agg_bwd_rows_row<H, C, ACT>(i, g, y, bias, out2, dout, ldq, row_stats);
 }
 
-// ---- destination side, stand-alone gathering form (gat_bwd.hip agg_bwd_dst_h2c256_kernel) --------
 template <int H, int C>
 __global__ __launch_bounds__(256) void agg_bwd_dst_generic_kernel(
     const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
     const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
     const float *__restrict__ dout, float ns, float *__restrict__ row_stats) {
-  using S = Shape<H, C>;
-  constexpr int U = S::UDst, V = S::V, Q = S::Q, HP = S::HP, NV = HP * U, G = 64 / NV;
-  const int lane = lane_id();
-  const bool upper = lane >= 32;
   const int i = row_begin + xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_in_block();
   if (i >= row_end) return;
-  const int beg = rowptr[i], end = rowptr[i + 1];
-  const float4 *h4 = reinterpret_cast<const float4 *>(h);
-  const float4 *g4 = reinterpret_cast<const float4 *>(dout) + (size_t)i * Q + lane;
-  float4 d[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) d[v] = g4[64 * v];
-  // after transpose_reduce<NV> over values [head * U + slot], the G lanes [idx * G, (idx + 1) * G) hold
-  // the sum of value idx; the first of them is its owner
-  const int idx = lane / G, myh = idx / U, kk = idx % U;
-  const bool owner = (lane % G) == 0 && myh < H;
-  float *rs = row_stats + (size_t)i * 4 * H;
-  float ad[H], mx[H], den[H];
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) {
-    ad[hh] = a_dst[(size_t)i * H + hh];
-    mx[hh] = rs[hh];
-    den[hh] = rs[H + hh] + 1e-16f;
-  }
-  float S1 = 0.f, S2 = 0.f, S3 = 0.f;
-  for (int base = beg; base < end; base += 64) {
-    const int e = base + lane;
-    int j = i;
-    float al[H], alp[H];
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) al[hh] = alp[hh] = 0.f;
-    if (e < end) {
-      j = col[e];
-      const float *as = a_src + (size_t)j * H;
-#pragma unroll
-      for (int hh = 0; hh < H; ++hh) {
-        const float ee = as[hh] + ad[hh];
-        al[hh] = expf(lrelu(ee, ns) - mx[hh]) / den[hh];
-        alp[hh] = al[hh] * (ee > 0.f ? 1.f : ns);
-      }
-    }
-    const int cnt = min(64, end - base);
-    for (int k = 0; k < cnt; k += U) {
-      float4 gth[U][V];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const size_t jj = (size_t)readlane_i(j, k + u);
-#pragma unroll
-        for (int v = 0; v < V; ++v) gth[u][v] = h4[jj * Q + 64 * v + lane];
-      }
-      float val[NV];
-#pragma unroll
-      for (int q = 0; q < NV; ++q) val[q] = 0.f;
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int v = 0; v < V; ++v) scatter_add<H, C>(val, U, u, v, upper, f4_dot(d[v], gth[u][v]));
-      transpose_reduce<NV>(val, lane);
-      const int src = k + kk;
-      float a = 0.f, ap = 0.f;
-#pragma unroll
-      for (int hh = 0; hh < H; ++hh) {
-        const float x = __shfl(al[hh], src), xp = __shfl(alp[hh], src);
-        a = myh == hh ? x : a;
-        ap = myh == hh ? xp : ap;
-      }
-      if (owner && src < cnt) {
-        S1 = fmaf(a, val[0], S1);
-        S2 = fmaf(ap, val[0], S2);
-        S3 += ap;
-      }
-    }
-  }
-  // the owners of head hh are among lanes [hh * 64 / HP, (hh + 1) * 64 / HP): sum within that group
-#pragma unroll
-  for (int o = 32 / HP; o > 0; o >>= 1) {
-    S1 += __shfl_xor(S1, o);
-    S2 += __shfl_xor(S2, o);
-    S3 += __shfl_xor(S3, o);
-  }
-  const float dd = S2 - S1 * S3;
-  float dl[H], da[H];
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) {
-    dl[hh] = readlane_f(S1, hh * (64 / HP));
-    da[hh] = readlane_f(dd, hh * (64 / HP));
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) {
-      rs[2 * H + hh] = dl[hh];
-      rs[3 * H + hh] = da[hh];
-    }
-  }
+  agg_bwd_dst_row<H, C>(i, rowptr, col, h, a_src, a_dst, dout, ns, row_stats);
 }
 
-// ---- source side (gat_bwd.hip agg_bwd_src_row) ----------------------------------------------------
 template <int H, int C, bool REMAP>
 __global__ __launch_bounds__(256) void agg_bwd_src_generic_kernel(
     const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
@@ -355,98 +53,17 @@ __global__ __launch_bounds__(256) void agg_bwd_src_generic_kernel(
     const float *__restrict__ row_stats, int64_t ldr, const float *__restrict__ dout, int64_t ldq,
     const float *__restrict__ att_s, const float *__restrict__ att_d, float ns,
     float *__restrict__ dh, float *__restrict__ da_src) {
-  // ldq: dout row stride in float4, ldr: row_stats row stride in floats
-  using S = Shape<H, C>;
-  constexpr int U = S::USrc, V = S::V, Q = S::Q, TR = S::TR, HP = S::HP;
-  const int lane = lane_id();
-  const bool upper = lane >= 32;
   const int r = row_begin + (REMAP ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x) * 4 + wave_in_block();
   if (r >= row_end) return;
-  const int beg = rowptr[r], end = rowptr[r + 1];
-  const float4 *h4 = reinterpret_cast<const float4 *>(h);
-  const float4 *g4 = reinterpret_cast<const float4 *>(dout);
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float asr[H], sb[H];
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) {
-    asr[hh] = a_src[(size_t)r * H + hh];
-    sb[hh] = 0.f;
-  }
-  float4 acc[V], c[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) acc[v] = c[v] = z4;
-  for (int base = beg; base < end; base += 64) {
-    const int e = base + lane;
-    int inb = r;
-    float al[H], A[H];
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) al[hh] = A[hh] = 0.f;
-    if (e < end) {
-      inb = col[e];
-      const float *ad = a_dst + (size_t)inb * H;
-      const float *rs = row_stats + ldr * inb;   // max[H] sum[H] delta[H] da_dst[H]
-#pragma unroll
-      for (int hh = 0; hh < H; ++hh) {
-        const float ee = asr[hh] + ad[hh];
-        al[hh] = expf(lrelu(ee, ns) - rs[hh]) / (rs[H + hh] + 1e-16f);
-        A[hh] = al[hh] * (ee > 0.f ? 1.f : ns);
-        sb[hh] = fmaf(A[hh], rs[2 * H + hh], sb[hh]);
-      }
-    }
-    const int cnt = min(64, end - base);
-    for (int k = 0; k < cnt; k += U) {
-      float4 gth[U][V];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const size_t ii = (size_t)readlane_i(inb, k + u);
-#pragma unroll
-        for (int v = 0; v < V; ++v) gth[u][v] = g4[ii * ldq + 64 * v + lane];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          acc[v] = f4_fma(bcast_pick<H, C>(al, k + u, v, upper), gth[u][v], acc[v]);
-          c[v] = f4_fma(bcast_pick<H, C>(A, k + u, v, upper), gth[u][v], c[v]);
-        }
-      }
-    }
-  }
-  float val[TR];   // [hh]: <sum alpha s dout_i, h_r> of head hh, [HP + hh]: sum alpha s delta_i
-#pragma unroll
-  for (int k = 0; k < TR; ++k) val[k] = 0.f;
-#pragma unroll
-  for (int v = 0; v < V; ++v)
-    scatter_add<H, C>(val, 1, 0, v, upper, f4_dot(c[v], h4[(size_t)r * Q + 64 * v + lane]));
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) val[HP + hh] = sb[hh];
-  transpose_reduce<TR>(val, lane);
-  float ds[H], dd[H];
-#pragma unroll
-  for (int hh = 0; hh < H; ++hh) {
-    ds[hh] = readlane_f(val[0], hh * (64 / TR)) - readlane_f(val[0], (HP + hh) * (64 / TR));
-    dd[hh] = row_stats[ldr * r + 3 * H + hh];
-  }
-  const float4 *s4 = reinterpret_cast<const float4 *>(att_s);
-  const float4 *t4 = reinterpret_cast<const float4 *>(att_d);
-  float4 *o4 = reinterpret_cast<float4 *>(dh) + (size_t)r * Q + lane;
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    float4 a = f4_fma(pick<H, C>(ds, v, upper), s4[64 * v + lane], acc[v]);
-    a = f4_fma(pick<H, C>(dd, v, upper), t4[64 * v + lane], a);
-    o4[64 * v] = a;
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int hh = 0; hh < H; ++hh) da_src[(size_t)r * H + hh] = ds[hh];
-  }
+  agg_bwd_src_row<H, C, false>(r, rowptr, col, h, a_src, a_dst, row_stats, ldr, dout, ldq, att_s, att_d, ns, dh,
+                               da_src);
 }
 
 // every supported (H, C) but (2, 256)
 #define HICGAT_GAT_SHAPES(X) X(1, 256) X(1, 512) X(1, 768) X(1, 1024) X(2, 128) X(2, 384) X(2, 512) X(3, 256) \
   X(4, 128) X(4, 256)
 
-// The supported-shape rule (include/hicgat.h); (2, 256) is in it and has its own kernels.
+// The supported-shape rule (include/hicgat.h); (2, 256) is in it and has its own entry kernels.
 bool gat_shape_supported(int H, int C) {
   return H >= 1 && H <= 4 && C > 0 && C % 128 == 0 && (H * C) % 256 == 0 && H * C <= 1024;
 }

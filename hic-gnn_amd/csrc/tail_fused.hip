@@ -509,7 +509,7 @@ __device__ __forceinline__ void ln_bwd_rows(const float *__restrict__ Dz, int ld
 // ROWS (the single-GPU h-first GATConv, gat_fwd.hip's training form): the GATConv's gather-free
 // rows backward (hicgat_gat_agg_bwd_rows, gat_bwd.hip) on the dx rows while they are in LDS -- dout
 // = dx [y > 0] (act) or dx into dout, delta^h = <dout^h, y^h - b^h> and da_dst^h = <dout^h, out2^h>
-// - delta^h S3^h into row_stats[8r + 4 .. 8r + 8), with the same arithmetic as agg_bwd_rows_kernel
+// - delta^h S3^h into row_stats[8r + 4 .. 8r + 8), with the same arithmetic as agg_bwd_rows_row<2, 256>
 // (bitwise) -- instead of writing dx for a separate pass that reads it back.  Y0 = y (the GATConv's
 // relu output: the tail's input), bh = its bias, out2 = sum alpha lrelu' h; each wave's row of y /
 // out2 is loaded at the kernel's start and held to the end.
@@ -602,7 +602,7 @@ __global__ __launch_bounds__(64 * NW) HICGAT_TAIL_WPE void tail_bwd_kernel(
   if constexpr (ROWS) {
     __syncthreads();
     const int row = m0 + wv;
-    if (row < M) {   // wave-uniform; agg_bwd_rows_kernel's arithmetic on the LDS dx row
+    if (row < M) {   // wave-uniform; agg_bwd_rows_row<2, 256>'s arithmetic (gat_agg.hpp) on the LDS dx row
       float4 d0 = *reinterpret_cast<const float4 *>(&As[wv * XS + 4 * lane]);
       float4 d1 = *reinterpret_cast<const float4 *>(&As[wv * XS + 256 + 4 * lane]);
       const float4 b0 = reinterpret_cast<const float4 *>(bh)[lane], b1 = reinterpret_cast<const float4 *>(bh)[64 + lane];

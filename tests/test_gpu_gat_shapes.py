@@ -181,7 +181,7 @@ def _kernel_inputs(H, C, n, density, seed):
 
 
 @pytest.mark.parametrize("act", [0, 1])
-@pytest.mark.parametrize("H,C", [(2, 128), (1, 512), (4, 256)])
+@pytest.mark.parametrize("H,C", [(2, 128), (1, 512), (4, 256), (2, 256)])
 def test_shapes_bwd_rows_equals_gather_dst(H, C, act):
     import hicgat
     K = hicgat.kernels.default()
@@ -205,7 +205,7 @@ def test_shapes_bwd_rows_equals_gather_dst(H, C, act):
         assert e < 2e-5, (k, e)
 
 
-@pytest.mark.parametrize("H,C", [(2, 128), (2, 512)])
+@pytest.mark.parametrize("H,C", [(2, 128), (2, 512), (2, 256)])
 def test_shapes_row_ranges_and_determinism(H, C):
     """[0, 100) + [100, 257) launches write the bits of one [0, 257) launch (forward and source
     pass); so does a second identical call."""

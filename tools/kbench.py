@@ -143,7 +143,9 @@ def main():
             bts = bench.agg_bytes(kb, n, nnz, d=H * C, h=H) if kb.startswith("gat_") else bench.agg_bytes(kb, n, nnz)
             alg = f"{bts / (min(ts) * 1e-3) / 1e9:9.0f} GB/s alg"
         tag = jname if flagship else f"{jname}@h{H}c{C}"
-        print(f"{lname:28s} {tag:22s} med {np.median(ts):8.4f} ms  min {min(ts):8.4f} ms  {alg}", flush=True)
+        rounds = " ".join(f"{t:.4f}" for t in ts)
+        print(f"{lname:28s} {tag:22s} med {np.median(ts):8.4f} ms  min {min(ts):8.4f} ms  {alg}  rounds {rounds}",
+              flush=True)
 
 
 if __name__ == "__main__":
