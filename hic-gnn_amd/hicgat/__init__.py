@@ -7,6 +7,10 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
                                               ~ models.py:614-691 / :1010-1047 / :14-55
   hicgat.gat_models.GATNetHeadsChangedLeakyReLU / GATNetReduced (eval only)
                                               ~ models.py:181-222 / :1414-1459
+  hicgat.gat_models.GATNet / GATNetHeadsChanged3LayersLeakyReLU /
+      GATNetHeadsChanged4LayerEmbedding512Dense / GATNetMoreReduced (trained with feature dropout)
+                                              ~ models.py:60-98 / :971-1007 / :1365-1411 / :1461-1494
+  hicgat.ops.act_dropout, hicgat.DropoutState ~ x.relu() / F.leaky_relu(x) -> torch.nn.Dropout(p)
   hicgat.graph.load_input / cont2dist / convert_to_matrix / Adj
                                               ~ utils.py:10-80 (+ torch_sparse.SparseTensor)
   hicgat.train.train / main                   ~ HiC-GNN_main.py:107-160
@@ -16,9 +20,13 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
   hicgat.embed.node2vec                       ~ Node2Vec(...).fit(...) at HiC_GAT_generalize_directly.py:150-155
 Compute runs in libhicgat.so (include/hicgat.h); there is no CPU fallback.
 """
-from . import _lib, align, dist, embed, graph, graphs, io, kernels, kr, metrics, nn, ops, optim, synth, train  # noqa: F401
-from .gat_models import (GATNetHeadsChanged3LayersLeakyReLUv2,  # noqa: F401
-                         GATNetHeadsChangedLeakyReLU, GATNetReduced,
+from . import (_lib, align, dist, dropout, embed, graph, graphs, io, kernels, kr, metrics, nn, ops, optim, synth,  # noqa: F401
+               train)
+from .dropout import DropoutState  # noqa: F401
+from .gat_models import (GATNet, GATNetHeadsChanged3LayersLeakyReLU,  # noqa: F401
+                         GATNetHeadsChanged3LayersLeakyReLUv2,
+                         GATNetHeadsChanged4LayerEmbedding512Dense,
+                         GATNetHeadsChangedLeakyReLU, GATNetMoreReduced, GATNetReduced,
                          GATNetSelectiveResidualsUpdated, MODELS, Net)
 from .graph import Adj, Data, Truth, cont2dist, convert_to_matrix, load_input  # noqa: F401
 from .nn import GATConv, SAGEConv  # noqa: F401

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("HICGAT_LIB", os.path.join(_HERE, "libhicgat.so"))
 
 c_int, c_i64, c_f, c_d, c_sz, c_p = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double,
                                      ctypes.c_size_t, ctypes.c_void_p)
-c_u64 = ctypes.c_uint64
+c_u64, c_u32 = ctypes.c_uint64, ctypes.c_uint32
 
 
 class WgradJob(ctypes.Structure):
@@ -156,6 +156,11 @@ SIGNATURES = {
     "hicgat_adam_step_table_ex": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_p, c_i64, c_p, c_int, c_p]),
     "hicgat_step_begin": (c_int, [c_p, c_i64, c_p, c_p]),
     "hicgat_step_begin_pack": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "hicgat_act_dropout_fwd": (c_int, [c_p, c_i64, c_int, c_int, c_int, c_f, c_d, c_u64, c_p, c_i64, c_u32, c_i64,
+                                       c_p, c_i64, c_p]),
+    "hicgat_act_dropout_bwd": (c_int, [c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_f, c_d, c_p, c_i64, c_p]),
+    "hicgat_dropout_mask": (c_int, [c_p, c_int, c_int, c_d, c_u64, c_p, c_i64, c_u32, c_i64, c_p]),
+    "hicgat_dropout_advance": (c_int, [c_p, c_p]),
     "hicgat_sim_collective": (c_int, [c_f, c_int, c_int, c_p]),
     "hicgat_stream_create": (c_int, [c_int, ctypes.POINTER(c_p)]),
     "hicgat_wall_stamp": (c_int, [c_p, c_int, c_p]),

@@ -382,6 +382,10 @@ class ShardedTrainer:
             # written for this one layer
             raise NotImplementedError(f"ShardedTrainer runs models whose conv is GATConv(512, 256, heads=2); "
                                       f"{type(model).__name__}.conv has (in, out, heads) = {shape}")
+        if getattr(model, "drop_sites", 0):
+            # the sharded step runs model.tail / post_act on its own rows: it would train without dropout
+            raise NotImplementedError(f"ShardedTrainer does not run feature dropout; {type(model).__name__} trains "
+                                      f"with Dropout at {model.drop_sites} sites (single-GPU hicgat.train only)")
         if kern is None:
             from .kernels import default
             kern = default()

@@ -7,6 +7,20 @@
 * ``GATNetReduced``                         -- models.py:1414-1459, GATConv(512, 512, heads=2), the model
                                                evaluate.py:86 loads (806 403); inference only.
 
+Four models that train with feature dropout (``_DropoutMLP``; ``ops.act_dropout``, dropout.hip):
+
+* ``GATNet``                                    -- models.py:60-98, GATConv(512, 512), p = 0.3 at three
+                                                   sites (436 355).
+* ``GATNetHeadsChanged3LayersLeakyReLU``        -- models.py:971-1007, leaky_relu, p = 0.3 (428 291).
+* ``GATNetHeadsChanged4LayerEmbedding512Dense`` -- models.py:1365-1411, p = 0.3 (438 339); the model
+                                                   HiC-GNN_node2vec_conversion.py:134 trains.
+* ``GATNetMoreReduced``                         -- models.py:1461-1494, p = 0.4.
+
+As in the reference, ``get_model`` never drops and ``forward`` / ``loss`` drop iff ``self.training``.
+The masks are not torch's: they are a counter-based function of (seed, step, site, row, column)
+(DESIGN.md "Feature dropout"), so a captured step replays them.  ``GATNetReduced`` still refuses to
+train: lifting that is a one-line follow-up together with the two tests that pin the refusal.
+
 Submodules are registered in the reference's order (so the same seed gives the same initial
 weights and the same state_dict keys).  ``forward`` returns the N x N distance matrix like the
 reference (``cdist`` on the GPU); ``get_model`` returns the N x 3 coordinates; ``loss`` is the
@@ -178,6 +192,133 @@ class GATNetReduced(_CoordsModel):
         return super().loss(x, edge_index, truth, kind, tile_range, stats)
 
 
+class _DropoutMLP(_CoordsModel):
+    """The zoo's commonest shape: conv -> act -> k Linears with ``act`` between them, and in the
+    training ``forward`` a Dropout after each of the first ``drop_sites`` activations (``get_model``
+    never drops).  A subclass registers its submodules in the reference's order and names its
+    Linears, in the order they run, in ``linears``.
+
+    Eval mode is the plain path (relu in the aggregation's epilogue).  In training mode ``forward``
+    and ``loss`` run the GATConv without an activation and each act -> dropout pair as one
+    ``ops.act_dropout``; the masks come from the model's ``DropoutState`` (created on the input's
+    device by the first training forward, seed = ``torch.initial_seed()``), which every training
+    forward advances once, first."""
+
+    act = "relu"        # or "leaky_relu" (slope 0.01)
+    drop_sites = 2
+    linears = ()
+
+    def _act(self, x):
+        return F.relu(x) if self.act == "relu" else F.leaky_relu(x)
+
+    def get_model(self, x, edge_index):
+        layers = [getattr(self, n) for n in self.linears]
+        if self.act == "relu":
+            x = self.conv(x, edge_index, act="relu")
+        else:
+            x = self._act(self.conv(x, edge_index))
+        for lin in layers[:-1]:
+            x = self._act(_lin(lin, x))
+        return _lin(layers[-1], x)
+
+    def dropout_state(self, device):
+        """The model's ``DropoutState`` (made on first use; ``p`` from ``self.dropout``)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        st = getattr(self, "_dropout_state", None)
+        if st is None or st.device != device:
+            from .dropout import DropoutState
+            st = self._dropout_state = DropoutState(device, p=self.dropout.p)
+        return st
+
+    def train_coords(self, x, edge_index):
+        """The coordinates of one training forward (models.py ``forward`` before its cdist)."""
+        st = self.dropout_state(x.device)
+        st.advance()
+        x = self.conv(x, edge_index, act=None)
+        for k, name in enumerate(self.linears):
+            x = ops.act_dropout(x, self.act, st.p, st, site=k) if k < self.drop_sites else self._act(x)
+            x = _lin(getattr(self, name), x)
+        return x
+
+    def _coords(self, x, edge_index):
+        return self.train_coords(x, edge_index) if self.training else self.get_model(x, edge_index)
+
+    def forward(self, x, edge_index):
+        return ops.pairwise_dist(self._coords(x, edge_index))
+
+    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None):
+        coords = self._coords(x, edge_index)
+        loss, stats = ops.fused_dist_loss(coords, truth, kind, tile_range, stats)
+        return loss, stats, coords
+
+
+class GATNet(_DropoutMLP):
+    """models.py:60-98: GATConv(512, 512) -> 512-256-128-64-3, relu, Dropout(0.3) after the first three
+    activations (436 355 parameters)."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 512)
+        self.densea = Linear(512, 256)
+        self.dense1 = Linear(256, 128)
+        self.dense2 = Linear(128, 64)
+        self.dense3 = Linear(64, 3)
+        self.dropout = Dropout(p=0.3)
+
+    drop_sites = 3
+    linears = ("densea", "dense1", "dense2", "dense3")
+
+
+class GATNetHeadsChanged3LayersLeakyReLU(_DropoutMLP):
+    """models.py:971-1007: GATConv(512, 256, heads=2) -> 512-256-128-3, leaky_relu(0.01), Dropout(0.3)
+    after the first two activations (428 291 parameters)."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 256, heads=2, concat=True)
+        self.densea = Linear(512, 256)
+        self.dense1 = Linear(256, 128)
+        self.dense2 = Linear(128, 3)
+        self.dropout = Dropout(p=0.3)
+
+    act = "leaky_relu"
+    linears = ("densea", "dense1", "dense2")
+
+
+class GATNetHeadsChanged4LayerEmbedding512Dense(_DropoutMLP):
+    """models.py:1365-1411, the model HiC-GNN_node2vec_conversion.py:134 trains: GATConv(512, 256,
+    heads=2) -> 512-256-128-64-32-3, relu, Dropout(0.3) after the first two activations (438 339)."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 256, heads=2, concat=True)
+        self.densea = Linear(512, 256)
+        self.dense1 = Linear(256, 128)
+        self.dense2 = Linear(128, 64)
+        self.dense3 = Linear(64, 32)
+        self.dense4 = Linear(32, 3)
+        self.dropout = Dropout(p=0.3)
+
+    linears = ("densea", "dense1", "dense2", "dense3", "dense4")
+
+
+class GATNetMoreReduced(_DropoutMLP):
+    """models.py:1461-1494: GATConv(512, 256, heads=2) -> 512-128-32-3, relu, Dropout(0.4) after the
+    first two activations."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 256, heads=2, concat=True)
+        self.densea = Linear(512, 128)
+        self.dense1 = Linear(128, 32)
+        self.dense2 = Linear(32, 3)
+        self.dropout = Dropout(p=0.4)
+
+    linears = ("densea", "dense1", "dense2")
+
+
 class Net(_CoordsModel):
     """models.py:14-55: SAGEConv(512, 512) -> relu -> 512-256-128-64-3 with relu between."""
 
@@ -203,4 +344,8 @@ MODELS = {
     "Net": Net,
     "GATNetHeadsChangedLeakyReLU": GATNetHeadsChangedLeakyReLU,
     "GATNetReduced": GATNetReduced,
+    "GATNet": GATNet,
+    "GATNetHeadsChanged3LayersLeakyReLU": GATNetHeadsChanged3LayersLeakyReLU,
+    "GATNetHeadsChanged4LayerEmbedding512Dense": GATNetHeadsChanged4LayerEmbedding512Dense,
+    "GATNetMoreReduced": GATNetMoreReduced,
 }

@@ -630,6 +630,43 @@ class HipKernels:
         _lib.check(self.lib.hicgat_ln_relu_res_bwd_params(W, P(dgamma), P(dbeta), int(accumulate), P(ws), ws.numel(),
                                                           _lib.stream(ws.device)), "hicgat_ln_relu_res_bwd_params")
 
+    # -- feature dropout (dropout.hip): act -> Dropout with a counter-based mask -------------------
+    ACT_NONE, ACT_RELU, ACT_LEAKY_RELU = 0, 1, 2   # include/hicgat.h HICGAT_ACT_*
+
+    def act_dropout_fwd(self, x, act, slope, p, seed, step_ctr, step_value, site, row_offset, y):
+        """y = kept ? act(x) * scale : 0 (``y`` may be ``x``); the step comes from the device count
+        ``step_ctr`` (int64 [1]) or, if that is None, from ``step_value``.  Rows may be strided."""
+        M, W = x.shape
+        assert y.shape == x.shape and x.stride(1) == 1 and y.stride(1) == 1
+        with _timed("act_dropout_fwd"):
+            _lib.check(self.lib.hicgat_act_dropout_fwd(P(x), x.stride(0), M, W, int(act), float(slope), float(p),
+                                                       int(seed), P(step_ctr), int(step_value), int(site),
+                                                       int(row_offset), P(y), y.stride(0), _lib.stream(x.device)),
+                       "hicgat_act_dropout_fwd")
+        return y
+
+    def act_dropout_bwd(self, dy, y, act, slope, p, dx):
+        """dx from dy and the forward's output y (``dx`` may be ``dy``)."""
+        M, W = y.shape
+        assert dy.shape == y.shape == dx.shape and dy.stride(1) == 1 and y.stride(1) == 1 and dx.stride(1) == 1
+        with _timed("act_dropout_bwd"):
+            _lib.check(self.lib.hicgat_act_dropout_bwd(P(dy), dy.stride(0), P(y), y.stride(0), M, W, int(act),
+                                                       float(slope), float(p), P(dx), dx.stride(0),
+                                                       _lib.stream(y.device)), "hicgat_act_dropout_bwd")
+        return dx
+
+    def dropout_mask(self, mask, p, seed, step_ctr, step_value, site, row_offset):
+        """The keep mask of the forward's device function into ``mask`` (contiguous uint8 [M, W])."""
+        M, W = mask.shape
+        assert mask.dtype == torch.uint8 and mask.is_contiguous()
+        _lib.check(self.lib.hicgat_dropout_mask(P(mask), M, W, float(p), int(seed), P(step_ctr), int(step_value),
+                                                int(site), int(row_offset), _lib.stream(mask.device)),
+                   "hicgat_dropout_mask")
+        return mask
+
+    def dropout_advance(self, counter):
+        _lib.check(self.lib.hicgat_dropout_advance(P(counter), _lib.stream(counter.device)), "hicgat_dropout_advance")
+
     # -- a10 --------------------------------------------------------------------------------------
     def adam_table(self, flat, grad, m, v, n, b1, b2, eps, table, step_ctr, counted=False):
         with _timed("adam"):

@@ -497,6 +497,83 @@ def linear(x, W, b=None):
     return _LinearFn.apply(x, W, b)
 
 
+def _act_code(act):
+    """``None`` / "none", "relu", "leaky_relu" (slope 0.01, torch's default) or ("leaky_relu", slope)
+    -> (HICGAT_ACT_* code, slope)."""
+    if isinstance(act, tuple) and len(act) == 2 and act[0] == "leaky_relu":
+        return kernels.HipKernels.ACT_LEAKY_RELU, float(act[1])
+    if act in (None, "none"):
+        return kernels.HipKernels.ACT_NONE, 0.0
+    if act == "relu":
+        return kernels.HipKernels.ACT_RELU, 0.0
+    if act == "leaky_relu":
+        return kernels.HipKernels.ACT_LEAKY_RELU, 0.01
+    raise ValueError(f"act must be None, 'relu', 'leaky_relu' or ('leaky_relu', slope); got {act!r}")
+
+
+def _rows16(t):
+    """``t`` as the dropout kernels read it: unit column stride, rows a multiple of 4 floats apart,
+    16-byte aligned (a copy only if it is not)."""
+    if t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous()
+
+
+class _ActDropoutFn(torch.autograd.Function):
+    """act -> Dropout(p) as one pass (dropout.hip); saves only its output: the backward reads the
+    activation's branch and the mask from y's sign (include/hicgat.h hicgat_act_dropout_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, act, slope, p, state, site, row_offset):
+        K = kernels.default()
+        x = _rows16(x)
+        y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        K.act_dropout_fwd(x, act, slope, p, state.seed, state.counter, 0, site, row_offset, y)
+        ctx.save_for_backward(y)
+        ctx.cfg = (act, slope, p)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, = ctx.saved_tensors
+        act, slope, p = ctx.cfg
+        dy = _rows16(dy)
+        dx = kernels.default().act_dropout_bwd(dy, y, act, slope, p, torch.empty_like(y))
+        return dx, None, None, None, None, None, None
+
+
+def act_dropout(x, act, p, state, site, row_offset=0):
+    """dropout(act(x), p) of a training forward: ``y = kept ? act(x) / (1 - p) : 0`` with the mask of
+    (state.seed, the state's device step count, site, row_offset + row, column) -- see
+    ``dropout.DropoutState``.  ``x``: float32 [rows, W] on the device, W % 4 == 0.  ``site``: the index
+    of this call within the forward; ``row_offset``: the global index of x's first row (a row shard
+    gets the bits of the whole tensor)."""
+    from .dropout import check_p
+    p = check_p(p)
+    code, slope = _act_code(act)
+    _dev_check(x)
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] % 4:
+        raise ValueError(f"act_dropout needs a float32 [rows, W] tensor with W % 4 == 0; got {x.dtype} "
+                         f"{tuple(x.shape)}")
+    if x.requires_grad and code == kernels.HipKernels.ACT_NONE:
+        raise NotImplementedError("act_dropout(act=None) has no backward (a zero output is ambiguous there)")
+    if int(site) < 0 or int(row_offset) < 0:
+        raise ValueError("site and row_offset must be >= 0")
+    return _ActDropoutFn.apply(x, code, slope, p, state, int(site), int(row_offset))
+
+
+def dropout_mask(rows, W, p, seed, step, site, row_offset=0, device="cuda"):
+    """The keep mask (bool [rows, W]) the dropout kernels use for these arguments (tests, tools)."""
+    from .dropout import check_p
+    p = check_p(p)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.HicgatUnavailable("hicgat ops need a CUDA (HIP) device; got " + str(device))
+    m = torch.empty((int(rows), int(W)), dtype=torch.uint8, device=device)
+    kernels.default().dropout_mask(m, p, int(seed) & ((1 << 64) - 1), None, int(step), site, row_offset)
+    return m.bool()
+
+
 class _DualLinearFn(torch.autograd.Function):
     """Two Linear layers on the same input (models.py:638-639 / 646-647: dense* and align_dense*)
     as ONE GEMM over [W1; W2]: the input is read once; the backward adds both input gradients

@@ -637,6 +637,45 @@ int hicgat_step_begin(float *grad, int64_t n, int64_t *step_counter, hicgat_stre
 int hicgat_step_begin_pack(float *grad, int64_t n, int64_t *step_counter, const float *W1c, const float *W2c,
                            const float *Wh, void *pack, size_t pack_bytes, hicgat_stream_t stream);
 
+/* ---- feature dropout: act -> torch.nn.Dropout of the zoo's forward() (models.py:74-75, :983-984,
+ * :1379-1380, :1472-1473, ...) as one pass, with a counter-based mask ------------------------------
+ * The keep mask is a pure function of (seed, step, site, global row, column), so it is generated
+ * in the kernel, replays under a hipGraph (the step count is read from the device) and does not
+ * depend on the launch geometry or on how the rows are sharded.  Philox4x32-10 (multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85); for element (R, c) of a
+ * width-W tensor, R = row_offset + local row:
+ *   g = R * (W / 4) + c / 4 (uint64);  counter = (g & 0xffffffff, g >> 32, step & 0xffffffff, site);
+ *   key = (seed & 0xffffffff, seed >> 32);  the element uses output word r[c % 4];
+ *   kept iff r >= T,  T = min(floor(p * 2^32), 2^32 - 1);  kept values are multiplied by
+ *   scale = (float)(1.0 / (1.0 - p)) (one rounding from double; torch's own constant may differ by
+ *   an ulp, and its masks differ anyway).  0 <= p < 1 (else HICGAT_EINVAL); p = 0 keeps everything.
+ * step = *step_counter when the pointer is given (a device int64, e.g. the one
+ * hicgat_dropout_advance increments), else step_value.  W % 4 == 0 and every ld a multiple of 4
+ * (else HICGAT_EUNSUPPORTED), x / y / dy / dx 16-B aligned, step_counter 8-B aligned, mask 4-B
+ * aligned (else HICGAT_EINVAL); all of it checked before any launch.  M = 0 is a no-op. */
+enum { HICGAT_ACT_NONE = 0, HICGAT_ACT_RELU = 1, HICGAT_ACT_LEAKY_RELU = 2 };
+/* y[r][c] = kept ? act(x[r][c]) * scale : 0;  relu(x) = x <= 0 ? 0 : x,  leaky_relu(x) = x > 0 ? x :
+ * x * slope (fp32).  In place (y == x, ldy == ldx) is allowed. */
+int hicgat_act_dropout_fwd(const float *x, int64_t ldx, int M, int W, int act, float slope, double p, uint64_t seed,
+                           const int64_t *step_counter, int64_t step_value, uint32_t site, int64_t row_offset,
+                           float *y, int64_t ldy, hicgat_stream_t stream);
+/* dx from dy and the forward's OUTPUT y alone (no mask is stored or regenerated):
+ *   relu:        dx = y > 0 ? dy * scale : 0
+ *   leaky_relu:  dx = y > 0 ? dy * scale : y < 0 ? (dy * scale) * slope : 0      (slope > 0)
+ * which is torch autograd of where(mask, act(x), 0) * scale bit for bit, with ONE deviation: a kept
+ * element whose pre-activation is exactly 0.0 under leaky_relu gets 0 where torch gives
+ * slope * scale * dy (y == 0 cannot tell it from a dropped one).  act = none is refused
+ * (HICGAT_EUNSUPPORTED: y == 0 is ambiguous there and no model needs it), as is leaky_relu with
+ * slope <= 0 (HICGAT_EINVAL).  dx may alias dy. */
+int hicgat_act_dropout_bwd(const float *dy, int64_t lddy, const float *y, int64_t ldy, int M, int W, int act,
+                           float slope, double p, float *dx, int64_t lddx, hicgat_stream_t stream);
+/* mask[r * W + c] = kept ? 1 : 0 (uint8), from the same device function as the forward (tests, tools). */
+int hicgat_dropout_mask(uint8_t *mask, int M, int W, double p, uint64_t seed, const int64_t *step_counter,
+                        int64_t step_value, uint32_t site, int64_t row_offset, hicgat_stream_t stream);
+/* *counter += 1 (one wave, lane 0, an ordinary store): a training forward's first launch, so that
+ * every dropout site of the step, ordered after it, reads the same new count -- also in a replay. */
+int hicgat_dropout_advance(int64_t *counter, hicgat_stream_t stream);
+
 /* ---- measurement infrastructure (no reference counterpart) ----------------------------------
  * An emulated collective for the simulated P-rank step (bench.py --simulate-world,
  * hicgat.dist.SimComm): `workgroups` x `threads` threads resident on the device for `us`
