@@ -43,8 +43,11 @@ def train_step(model, opt, x, edge_index, truth, kind="mse", stats=None):
 GRAPH_WARMUP = 2   # eager steps before the step is captured (real training steps, in the history)
 
 
+LOSSES = ("mse", "combined", "contrastive", "mse+dscc")
+
+
 def train(model, data, truth, lr=1e-3, thresh=1e-8, steps=None, loss="mse", max_steps=1_000_000,
-          on_step=None, graph=None, dscc_history=None, print_interval=0):
+          on_step=None, graph=None, dscc_history=None, print_interval=0, alpha=1.0, mse_history=None):
     """Returns (optimizer, per-step loss list).  ``truth`` is a ``graph.Truth``.
 
     ``graph`` (default: on for device tensors): after ``GRAPH_WARMUP`` eager steps the step is
@@ -52,18 +55,43 @@ def train(model, data, truth, lr=1e-3, thresh=1e-8, steps=None, loss="mse", max_
     step for the ``lossdiff`` rule (HiC-GNN_main.py:128) -- replays give the same bits as eager steps.
     ``dscc_history`` (a list): the dSCC of every step's forward coordinates against the target, as
     HiC_GAT_generalize_directly.py:242-247 appends it; ``print_interval`` > 0 prints its progress line
-    (:256) every that many steps."""
+    (:256) every that many steps.  The score is ``metrics.DsccScorer``'s, built once for the run; it
+    runs INSIDE the step (so inside the captured graph) and its rho rides in the same device buffer
+    as the loss value: still one device -> host read per step.
+
+    ``loss="mse+dscc"`` is the combined_loss_training.py:106-146 objective: the recorded value is
+    MSE + ``alpha`` * (1 - rho) with a NaN rho replaced by 0 (:136-138), the gradient is the MSE's
+    (the Spearman term is detached there too), rho is scored on ``model.get_model``'s coordinates
+    (:132-133: the step's own for a model without dropout sites, a second no-grad forward for a
+    ``_DropoutMLP``); fixed ``steps`` gives the script's epoch loop.  ``dscc_history`` then receives
+    each step's rho and ``mse_history`` (a list) the MSE part."""
     from .graphs import CapturedStep
+    if loss not in LOSSES:       # a KeyError, as ops.LOSS_KINDS[kind] raises for the fused kinds
+        raise KeyError(f"unknown loss {loss!r}: one of {', '.join(LOSSES)}")
+    with_dscc = loss == "mse+dscc"
+    kind = "mse" if with_dscc else loss
     opt = FlatAdam(model.flat_parameters(), lr=lr)
     use_graph = data.x.is_cuda if graph is None else bool(graph)
     if use_graph:
         opt.enable_device_step()
     old, diff, hist = 1.0, 1.0, []
     stats = torch.empty(12, dtype=torch.float64, device=data.x.device)
-    score = truth.scoring() if dscc_history is not None else None
+    scorer = metrics.DsccScorer(truth.scoring()) if (dscc_history is not None or with_dscc) else None
+    # (rho, sum b^2, tie groups, NaN flag, the step's loss value): what the host reads per step
+    host = torch.zeros(5, dtype=torch.float64, device=data.x.device) if scorer is not None else None
+    from .gat_models import _DropoutMLP
+    rescore = with_dscc and isinstance(model, _DropoutMLP)
 
     def step():
-        return train_step(model, opt, data.x, data.edge_index, truth, loss, stats)
+        scored = None
+        if rescore:      # :132 get_model never drops; run on this step's parameters, before their update
+            with torch.no_grad():
+                scored = model.get_model(data.x, data.edge_index).contiguous()
+        val, st, coords = train_step(model, opt, data.x, data.edge_index, truth, kind, stats)
+        if scorer is not None:
+            host[4].copy_(st[10] if kind == "contrastive" else val.detach())
+            scorer.score_into(coords.detach().contiguous() if scored is None else scored, host)
+        return val, st, coords
 
     replay = None
     while (diff > thresh if steps is None else len(hist) < steps) and len(hist) < max_steps:
@@ -71,12 +99,19 @@ def train(model, data, truth, lr=1e-3, thresh=1e-8, steps=None, loss="mse", max_
             replay = CapturedStep(step, warmup=0)     # captured, not run: the replay below is this step
         val, st, coords = replay() if replay is not None else step()
         # the one device -> host read per step (the contrastive total is float64 in the reference)
-        lv = float(st[10].item()) if loss == "contrastive" else float(val.item())
+        if scorer is not None:
+            rho, _, _, _, lv = host.tolist()
+        else:
+            lv = float(st[10].item()) if loss == "contrastive" else float(val.item())
+        if with_dscc:
+            if mse_history is not None:
+                mse_history.append(lv)
+            lv = lv + alpha * (1.0 - (0.0 if rho != rho else rho))
         diff = abs(old - lv)
         old = lv
         hist.append(lv)
-        if score is not None:
-            dscc_history.append(metrics.dscc(coords, score))
+        if dscc_history is not None:
+            dscc_history.append(rho)
             if print_interval and (len(hist) - 1) % print_interval == 0:
                 print(f"Iteration [{len(hist) - 1}], Total Loss: {float(stats[7]):.6g}, dSCC: {dscc_history[-1]}, "
                       f"Loss Diff: {diff}")
@@ -117,7 +152,9 @@ def make_parser():
     p.add_argument("-th", "--threshold", type=float, default=1e-8)
     p.add_argument("--steps", type=int, default=None, help="fixed step count instead of the threshold rule")
     p.add_argument("--model", default="GATNetSelectiveResidualsUpdated", choices=sorted(MODELS))
-    p.add_argument("--loss", default="mse", choices=["mse", "combined", "contrastive"])
+    p.add_argument("--loss", default="mse", choices=list(LOSSES))
+    p.add_argument("--alpha", type=float, default=1.0, help="weight of the (1 - dSCC) term of --loss mse+dscc "
+                                                            "(combined_loss_training.py:142)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", default=None, help="prefix for <out>_weights.pt / _structure.pdb / _log.txt")
     p.add_argument("--no-kr", action="store_true", help="the input is already KR-normalised (skip KRnorm)")
@@ -157,7 +194,8 @@ def main(argv=None):
     for f in conv:
         print(f"Training model using conversion value {f}.")
         model = MODELS[a.model]().to(data.x.device)
-        _, hist = train(model, data, truth, a.learningrate, a.threshold, a.steps, a.loss)
+        extra = {"alpha": a.alpha} if a.loss == "mse+dscc" else {}
+        _, hist = train(model, data, truth, a.learningrate, a.threshold, a.steps, a.loss, **extra)
         coords = model.get_model(data.x.float(), data.edge_index).detach()
         rho = metrics.dscc(coords, truth.scoring())
         print(f"conversion {f}: steps {len(hist)} loss {hist[-1]:.6g} dSCC {rho:.6f}")

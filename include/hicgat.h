@@ -676,6 +676,38 @@ int hicgat_dropout_mask(uint8_t *mask, int M, int W, double p, uint64_t seed, co
  * every dropout site of the step, ordered after it, reads the same new count -- also in a replay. */
 int hicgat_dropout_advance(int64_t *counter, hicgat_stream_t stream);
 
+/* ---- Spearman / per-step dSCC (a11: scipy.stats.spearmanr of HiC_GAT_generalize_directly.py:242
+ * and combined_loss_training.py:135) ---------------------------------------------------------------
+ * Exact Spearman correlation with scipy's tie rule (a tie group shares its average rank), by a
+ * stable LSD radix sort (8-bit digits, four passes) of 32-bit keys with a 32-bit payload and one
+ * tie-aware reduction; no host sync, no allocation, no N x N matrix.  The key is the
+ * order-preserving image of the float's bits with -0 canonicalised to +0 (they tie); denormals stay
+ * distinct.  A NaN on either side gives rho = NaN (nan_policy = 'propagate'), as do a constant side
+ * and M < 2.  Ranks are DOUBLED average ranks (uint32, 2 <= rank2 <= 2 M), so every size needs
+ * M < 2^31: larger M returns HICGAT_EUNSUPPORTED before anything else is looked at.
+ * ws: 256-B aligned, the size the workspace query returns (0 for an unsupported M).  Two calls on the same inputs give the
+ * same bits (integer atomics only; fp64 sums in a fixed order).
+ *   side_stats [4] = (sum of a^2 with a = rank2 - (M + 1), number of tie groups, NaN flag, M)
+ *   out        [4] = (rho, sum of b^2 of the scored side, its number of tie groups, NaN flag) */
+/* keys per sort tile (tests place M around its multiples) */
+int hicgat_rank_tile(void);
+size_t hicgat_rank_workspace_bytes(int64_t M);
+/* rank2[k] = 2 * (average rank of v[k] among v[0..M)), in the input's element order; prepares one
+ * side (the truth) once. */
+int hicgat_avg_rank2(const float *v, int64_t M, uint32_t *rank2, double *side_stats, void *ws, size_t ws_bytes,
+                     hicgat_stream_t stream);
+/* v[k] = T[i * ld + j] for the k-th pair i < j of torch.triu_indices(N, N, 1) (row-major upper
+ * triangle); v holds N (N - 1) / 2 floats.  2 <= N <= 65536. */
+int hicgat_triu_gather(const float *T, int N, int64_t ld, float *v, hicgat_stream_t stream);
+/* Spearman of v against a side prepared by hicgat_avg_rank2 (same M, same element order). */
+int hicgat_spearman_vs_rank2(const float *v, const uint32_t *rank2, const double *side_stats, int64_t M, double *out,
+                             void *ws, size_t ws_bytes, hicgat_stream_t stream);
+/* dSCC of coords [N, 3] against the prepared upper triangle of the truth: pair k's distance is
+ * computed with the expression of hicgat_pairdist_fwd (the same bits) and goes straight into the
+ * sort's key; the distance matrix is never stored.  M = N (N - 1) / 2, 2 <= N <= 65536. */
+int hicgat_dscc_coords(const float *coords, int N, const uint32_t *rank2, const double *side_stats, double *out,
+                       void *ws, size_t ws_bytes, hicgat_stream_t stream);
+
 /* ---- measurement infrastructure (no reference counterpart) ----------------------------------
  * An emulated collective for the simulated P-rank step (bench.py --simulate-world,
  * hicgat.dist.SimComm): `workgroups` x `threads` threads resident on the device for `us`
