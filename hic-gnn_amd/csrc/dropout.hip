@@ -7,7 +7,7 @@
 // global row, column quad), never on which thread or block computes it, so the grid is free: at most
 // kMaxBlocks blocks stride over the quads, each thread carrying (row, quad) forward by a stride the
 // host split into whole rows and a remainder (no division in the loop).  No LDS, no scratch.
-#include "common.hpp"
+#include "philox.hpp"
 
 using namespace hicgat;
 
@@ -15,41 +15,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;   // 8 blocks per CU; the rest of a tall tensor is strided
-
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(kPhiloxM0, c.x), lo0 = kPhiloxM0 * c.x;
-    const uint32_t hi1 = __umulhi(kPhiloxM1, c.z), lo1 = kPhiloxM1 * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += kPhiloxW0;
-    k1 += kPhiloxW1;
-  }
-  return c;
-}
-
-// What a launch needs to know about the mask (by value: 40 bytes of kernel arguments).
-struct MaskArgs {
-  uint64_t seed;
-  const int64_t *step_counter;   // device; NULL: step_value
-  int64_t step_value;
-  int64_t row_offset;
-  uint32_t site, T;
-};
-
-__device__ __forceinline__ uint32_t mask_step(const MaskArgs &m) {
-  return (uint32_t)(m.step_counter ? *m.step_counter : m.step_value);
-}
-
-// The four random words of column quad `q` of global row `R` (W4 quads per row).
-__device__ __forceinline__ uint4 quad_words(const MaskArgs &m, uint32_t step, int64_t R, int W4, int q) {
-  const uint64_t g = (uint64_t)R * (uint64_t)W4 + (uint64_t)q;
-  return philox4x32_10(make_uint4((uint32_t)g, (uint32_t)(g >> 32), step, m.site), (uint32_t)m.seed,
-                       (uint32_t)(m.seed >> 32));
-}
 
 // The walk of one thread over the quads of an M x (4 W4) tensor: thread t starts at quad t of the
 // row-major quad order and moves on by gridDim.x * kThreads quads = drow rows + dq quads.
@@ -70,13 +35,6 @@ struct QuadWalk {
     }
   }
 };
-
-template <int ACT>
-__device__ __forceinline__ float act_apply(float x, float slope) {
-  if (ACT == HICGAT_ACT_RELU) return relu_t(x);
-  if (ACT == HICGAT_ACT_LEAKY_RELU) return lrelu(x, slope);
-  return x;
-}
 
 template <int ACT>
 __global__ __launch_bounds__(kThreads) void act_dropout_fwd_kernel(const float *x, int64_t ldx, int M, int W4,
@@ -105,15 +63,6 @@ __global__ __launch_bounds__(kThreads) void dropout_mask_kernel(uint8_t *mask, i
   }
 }
 
-// g = dy * scale is the gradient that reaches the activation's output (rounded once, as torch's
-// mul backward rounds it); the saved y's sign then selects the activation's branch.
-template <int ACT>
-__device__ __forceinline__ float act_dropout_grad(float dy, float y, float slope, float scale) {
-  const float g = dy * scale;
-  if (ACT == HICGAT_ACT_RELU) return y > 0.f ? g : 0.f;
-  return y > 0.f ? g : (y < 0.f ? g * slope : 0.f);
-}
-
 template <int ACT>
 __global__ __launch_bounds__(kThreads) void act_dropout_bwd_kernel(const float *dy, int64_t lddy, const float *y,
                                                                    int64_t ldy, int M, int W4, int drow, int dq,
@@ -138,17 +87,6 @@ __global__ __launch_bounds__(64) void dropout_advance_kernel(int64_t *counter) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-bool p_ok(double p) { return p >= 0.0 && p < 1.0; }   // false for NaN
-
-uint32_t keep_threshold(double p) {
-  const double t = __builtin_floor(p * 4294967296.0);
-  return t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
-}
-
-float keep_scale(double p) { return (float)(1.0 / (1.0 - p)); }
-
-bool misaligned(const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; }
-
 // Grid of the walk over M rows of W4 quads, and the stride of one step of it in rows + quads.
 struct Walk {
   int blocks, drow, dq;

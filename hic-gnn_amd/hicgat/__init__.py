@@ -10,6 +10,9 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
   hicgat.gat_models.GATNet / GATNetHeadsChanged3LayersLeakyReLU /
       GATNetHeadsChanged4LayerEmbedding512Dense / GATNetMoreReduced (trained with feature dropout)
                                               ~ models.py:60-98 / :971-1007 / :1365-1411 / :1461-1494
+  hicgat.gat_models.GATNetHeadsChanged4LayersLeakyReLU / GATNetHeadsChanged4LayersLeakyReLUHeads4
+      (BatchNorm1d + feature dropout)         ~ models.py:270-319 / :834-883
+  hicgat.ops.bn_act_dropout                   ~ torch.nn.BatchNorm1d -> F.leaky_relu -> torch.nn.Dropout(p)
   hicgat.ops.act_dropout, hicgat.DropoutState ~ x.relu() / F.leaky_relu(x) -> torch.nn.Dropout(p)
   hicgat.graph.load_input / cont2dist / convert_to_matrix / Adj
                                               ~ utils.py:10-80 (+ torch_sparse.SparseTensor)
@@ -26,6 +29,8 @@ from .dropout import DropoutState  # noqa: F401
 from .gat_models import (GATNet, GATNetHeadsChanged3LayersLeakyReLU,  # noqa: F401
                          GATNetHeadsChanged3LayersLeakyReLUv2,
                          GATNetHeadsChanged4LayerEmbedding512Dense,
+                         GATNetHeadsChanged4LayersLeakyReLU,
+                         GATNetHeadsChanged4LayersLeakyReLUHeads4,
                          GATNetHeadsChangedLeakyReLU, GATNetMoreReduced, GATNetReduced,
                          GATNetSelectiveResidualsUpdated, MODELS, Net)
 from .graph import Adj, Data, Truth, cont2dist, convert_to_matrix, load_input  # noqa: F401

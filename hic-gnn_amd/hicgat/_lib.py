@@ -161,6 +161,12 @@ SIGNATURES = {
     "hicgat_act_dropout_bwd": (c_int, [c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_f, c_d, c_p, c_i64, c_p]),
     "hicgat_dropout_mask": (c_int, [c_p, c_int, c_int, c_d, c_u64, c_p, c_i64, c_u32, c_i64, c_p]),
     "hicgat_dropout_advance": (c_int, [c_p, c_p]),
+    "hicgat_bn_workspace_bytes": (c_sz, [c_int, c_int]),
+    "hicgat_bn_stats": (c_int, [c_p, c_i64, c_int, c_int, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "hicgat_bn_act_dropout_fwd": (c_int, [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_d, c_int, c_f, c_d,
+                                          c_u64, c_p, c_i64, c_u32, c_i64, c_p, c_i64, c_p]),
+    "hicgat_bn_act_dropout_bwd": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_d,
+                                          c_int, c_f, c_d, c_p, c_i64, c_p, c_p, c_int, c_p, c_sz, c_p]),
     "hicgat_rank_tile": (c_int, []),
     "hicgat_rank_workspace_bytes": (c_sz, [c_i64]),
     "hicgat_avg_rank2": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_sz, c_p]),

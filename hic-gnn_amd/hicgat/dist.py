@@ -375,8 +375,13 @@ class SimComm:
 
 class ShardedTrainer:
     def __init__(self, model, x, adj, truth, lr=1e-3, kind="mse", group=None, kern=None, mode="auto", comm=None):
+        if any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in model.modules()):
+            # before any collective (and before the conv check, so both BatchNorm models say why): batch
+            # statistics over sharded rows would need a collective of their own
+            raise NotImplementedError(f"ShardedTrainer does not run batch normalisation; {type(model).__name__} "
+                                      f"normalises over all node rows (single-GPU hicgat.train only)")
         conv = getattr(model, "conv", None)
-        shape = tuple(getattr(conv, a, None) for a in ("in_channels", "out_channels", "heads"))
+        shape =tuple(getattr(conv, a, None) for a in ("in_channels", "out_channels", "heads"))
         if shape != (512, 256, 2):
             # before any collective: the sharded kernels (gat_xagg.hip, the packed all-gather rows) are
             # written for this one layer

@@ -16,6 +16,13 @@ Four models that train with feature dropout (``_DropoutMLP``; ``ops.act_dropout`
                                                    HiC-GNN_node2vec_conversion.py:134 trains.
 * ``GATNetMoreReduced``                         -- models.py:1461-1494, p = 0.4.
 
+Two more that also normalise with ``torch.nn.BatchNorm1d`` over the node rows (``_BatchNormMLP``;
+``ops.bn_act_dropout``, batchnorm.hip), Dropout(0.4) at two sites:
+
+* ``GATNetHeadsChanged4LayersLeakyReLU``       -- models.py:270-319 (437 251 parameters); the model
+                                                  tune_hyperparams_embeddings.py:48 scores.
+* ``GATNetHeadsChanged4LayersLeakyReLUHeads4`` -- models.py:834-883, GATConv(256, 256, heads=4) (569 859).
+
 As in the reference, ``get_model`` never drops and ``forward`` / ``loss`` drop iff ``self.training``.
 The masks are not torch's: they are a counter-based function of (seed, step, site, row, column)
 (DESIGN.md "Feature dropout"), so a captured step replays them.  ``GATNetReduced`` still refuses to
@@ -28,7 +35,7 @@ fused path used by the training loop (distance + MSE [+ Pearson] without materia
 """
 import torch
 import torch.nn.functional as F
-from torch.nn import Dropout, LayerNorm, LeakyReLU, Linear
+from torch.nn import BatchNorm1d, Dropout, LayerNorm, LeakyReLU, Linear
 
 from . import ops
 from .nn import GATConv, SAGEConv
@@ -319,6 +326,82 @@ class GATNetMoreReduced(_DropoutMLP):
     linears = ("densea", "dense1", "dense2")
 
 
+class _BatchNormMLP(_DropoutMLP):
+    """conv -> leaky_relu -> Dropout, then Linear -> BatchNorm1d -> leaky_relu (-> Dropout after the
+    first) per hidden layer, then the last Linear (models.py:270-319, :834-883).  ``norms`` names the
+    BatchNorm1d of each Linear but the last.  Dropout site 0 is the activation after the conv
+    (``ops.act_dropout``), site 1 the one after ``bn_a``; every BatchNorm stage is one
+    ``ops.bn_act_dropout`` (batchnorm.hip).
+
+    Dropout runs only in a training ``forward`` / ``loss`` and never in ``get_model``.  BatchNorm
+    follows ``self.training`` everywhere, ``get_model`` included: the reference's training scripts never
+    call ``eval()``, so there ``get_model`` normalises by batch statistics and moves the running buffers
+    (``num_batches_tracked`` counts it).  That is kept: call ``model.eval()`` for the running ones."""
+
+    act = "leaky_relu"
+    drop_sites = 2
+    norms = ()
+
+    def _mlp(self, x, st):
+        """From the (dropped) activation of the conv's output on; ``st``: the DropoutState or None."""
+        names = self.linears
+        for k, (lin, bn) in enumerate(zip(names[:-1], self.norms)):
+            drop = st is not None and k + 1 < self.drop_sites
+            x = ops.bn_act_dropout(_lin(getattr(self, lin), x), getattr(self, bn), self.act,
+                                   st if drop else None, k + 1 if drop else None)
+        return _lin(getattr(self, names[-1]), x)
+
+    def get_model(self, x, edge_index):
+        return self._mlp(self._act(self.conv(x, edge_index)), None)
+
+    def train_coords(self, x, edge_index):
+        st = self.dropout_state(x.device)
+        st.advance()
+        x = ops.act_dropout(self.conv(x, edge_index, act=None), self.act, st.p, st, site=0)
+        return self._mlp(x, st)
+
+
+class GATNetHeadsChanged4LayersLeakyReLU(_BatchNormMLP):
+    """models.py:270-319, the model tune_hyperparams_embeddings.py:48 loads: GATConv(512, 256, heads=2)
+    -> 512-256-128-64-3 with BatchNorm1d after the first three Linears, leaky_relu(0.01), Dropout(0.4)
+    after the conv's and bn_a's activations (437 251 parameters with the 896 of the BatchNorms)."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 256, heads=2, concat=True)
+        self.densea = Linear(512, 256)
+        self.bn_a = BatchNorm1d(256)
+        self.dense1 = Linear(256, 128)
+        self.bn1 = BatchNorm1d(128)
+        self.dense2 = Linear(128, 64)
+        self.bn2 = BatchNorm1d(64)
+        self.dense3 = Linear(64, 3)
+        self.dropout = Dropout(p=0.4)
+
+    linears = ("densea", "dense1", "dense2", "dense3")
+    norms = ("bn_a", "bn1", "bn2")
+
+
+class GATNetHeadsChanged4LayersLeakyReLUHeads4(_BatchNormMLP):
+    """models.py:834-883: GATConv(256, 256, heads=4) -> 1024-256-128-64-3, otherwise as
+    ``GATNetHeadsChanged4LayersLeakyReLU`` (569 859 parameters); 256 feature columns."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(256, 256, heads=4, concat=True)
+        self.densea = Linear(1024, 256)
+        self.bn_a = BatchNorm1d(256)
+        self.dense1 = Linear(256, 128)
+        self.bn1 = BatchNorm1d(128)
+        self.dense2 = Linear(128, 64)
+        self.bn2 = BatchNorm1d(64)
+        self.dense3 = Linear(64, 3)
+        self.dropout = Dropout(p=0.4)
+
+    linears = ("densea", "dense1", "dense2", "dense3")
+    norms = ("bn_a", "bn1", "bn2")
+
+
 class Net(_CoordsModel):
     """models.py:14-55: SAGEConv(512, 512) -> relu -> 512-256-128-64-3 with relu between."""
 
@@ -348,4 +431,6 @@ MODELS = {
     "GATNetHeadsChanged3LayersLeakyReLU": GATNetHeadsChanged3LayersLeakyReLU,
     "GATNetHeadsChanged4LayerEmbedding512Dense": GATNetHeadsChanged4LayerEmbedding512Dense,
     "GATNetMoreReduced": GATNetMoreReduced,
+    "GATNetHeadsChanged4LayersLeakyReLU": GATNetHeadsChanged4LayersLeakyReLU,
+    "GATNetHeadsChanged4LayersLeakyReLUHeads4": GATNetHeadsChanged4LayersLeakyReLUHeads4,
 }

@@ -667,6 +667,55 @@ class HipKernels:
     def dropout_advance(self, counter):
         _lib.check(self.lib.hicgat_dropout_advance(P(counter), _lib.stream(counter.device)), "hicgat_dropout_advance")
 
+    # -- BatchNorm1d -> act -> Dropout (batchnorm.hip) ----------------------------------------------
+    def bn_workspace(self, M, W, device):
+        return _lib.workspace(self.lib.hicgat_bn_workspace_bytes(int(M), int(W)), device)
+
+    def bn_stats(self, y, eps, momentum, stats, running_mean, running_var, num_batches_tracked, ws=None):
+        """Batch statistics of y [M, W] into ``stats`` [4, W] = (mean, mean_lo, rstd, rstd_lo) and the training
+        forward's buffer updates (each buffer may be None), all on the device."""
+        M, W = y.shape
+        assert y.stride(1) == 1 and stats.shape == (4, W) and stats.is_contiguous()
+        if ws is None:
+            ws = self.bn_workspace(M, W, y.device)
+        with _timed("bn_stats"):
+            _lib.check(self.lib.hicgat_bn_stats(P(y), y.stride(0), M, W, float(eps), float(momentum), P(stats),
+                                                P(running_mean), P(running_var), P(num_batches_tracked), P(ws),
+                                                ws.numel(), _lib.stream(y.device)), "hicgat_bn_stats")
+        return stats
+
+    def bn_act_dropout_fwd(self, y, gamma, beta, stats, running_mean, running_var, eps, act, slope, p, seed, step_ctr,
+                           step_value, site, row_offset, z):
+        """z = dropout(act(BN(y))); ``stats`` None: eval mode (the running buffers).  Rows may be strided."""
+        M, W = y.shape
+        assert z.shape == y.shape and y.stride(1) == 1 and z.stride(1) == 1
+        with _timed("bn_act_dropout_fwd"):
+            _lib.check(self.lib.hicgat_bn_act_dropout_fwd(P(y), y.stride(0), M, W, P(gamma), P(beta), P(stats),
+                                                          P(running_mean), P(running_var), float(eps), int(act),
+                                                          float(slope), float(p), int(seed), P(step_ctr),
+                                                          int(step_value), int(site), int(row_offset), P(z),
+                                                          z.stride(0), _lib.stream(y.device)),
+                       "hicgat_bn_act_dropout_fwd")
+        return z
+
+    def bn_act_dropout_bwd(self, dz, z, y, gamma, stats, running_mean, running_var, eps, act, slope, p, dy, dgamma,
+                           dbeta, accumulate=False, ws=None):
+        """dy, and dgamma / dbeta (written or accumulated; both None: only left as the first 2 W floats
+        [dgamma | dbeta] of ``ws``).  ``z``: the forward's output (None for act = none)."""
+        M, W = y.shape
+        assert dz.shape == y.shape == dy.shape and dz.stride(1) == 1 and y.stride(1) == 1 and dy.stride(1) == 1
+        assert z is None or (z.shape == y.shape and z.stride(1) == 1)
+        if ws is None:
+            ws = self.bn_workspace(M, W, y.device)
+        with _timed("bn_act_dropout_bwd"):
+            _lib.check(self.lib.hicgat_bn_act_dropout_bwd(P(dz), dz.stride(0), P(z), 0 if z is None else z.stride(0),
+                                                          P(y), y.stride(0), M, W, P(gamma), P(stats),
+                                                          P(running_mean), P(running_var), float(eps), int(act),
+                                                          float(slope), float(p), P(dy), dy.stride(0), P(dgamma),
+                                                          P(dbeta), int(accumulate), P(ws), ws.numel(),
+                                                          _lib.stream(y.device)), "hicgat_bn_act_dropout_bwd")
+        return dy
+
     # -- a10 --------------------------------------------------------------------------------------
     def adam_table(self, flat, grad, m, v, n, b1, b2, eps, table, step_ctr, counted=False):
         with _timed("adam"):

@@ -662,6 +662,110 @@ def ln_relu_res(y, norm, res=None):
     return _LnReluResFn.apply(y, norm.weight, norm.bias, res, norm.eps)
 
 
+class _BnActDropoutFn(torch.autograd.Function):
+    """BatchNorm1d -> act -> Dropout(p) (batchnorm.hip; models.py:288-291).  A training-mode forward
+    takes the batch statistics (two launches), updates the module's buffers on the device and applies
+    in one pass; an eval-mode one is the apply pass alone on the running buffers.  Saves its input y,
+    the column statistics and its output z (the activation's branch and the mask are read from z's
+    sign, as in ``_ActDropoutFn``; nothing for act = none)."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, bn, act, slope, p, state, site, row_offset):
+        K = kernels.default()
+        y = _rows16(y)
+        M, W = y.shape
+        z = torch.empty((M, W), dtype=torch.float32, device=y.device)
+        stats = None
+        if bn.training:
+            stats = torch.empty((4, W), dtype=torch.float32, device=y.device)
+            K.bn_stats(y, bn.eps, bn.momentum, stats, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+        seed, ctr = (state.seed, state.counter) if p > 0.0 else (0, None)
+        K.bn_act_dropout_fwd(y, gamma, beta, stats, bn.running_mean, bn.running_var, bn.eps, act, slope, p, seed, ctr,
+                             0, site, row_offset, z)
+        saved = [y, gamma] + ([stats] if stats is not None else []) + ([z] if act != K.ACT_NONE else [])
+        ctx.save_for_backward(*saved)
+        ctx.cfg = (act, slope, p, bn.eps, stats is not None)
+        ctx.running = None if stats is not None else (bn.running_mean, bn.running_var)   # eval: fixed statistics
+        ctx.params = (gamma, beta)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        K = kernels.default()
+        act, slope, p, eps, batch = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        y, gamma = saved[:2]
+        stats = saved[2] if batch else None
+        z = saved[-1] if act != K.ACT_NONE else None
+        rm, rv = ctx.running if ctx.running is not None else (None, None)
+        dz = _rows16(dz)
+        M, W = y.shape
+        dy = torch.empty((M, W), dtype=torch.float32, device=y.device)
+        sg, sb = _sink(ctx.params[0]), _sink(ctx.params[1])
+        args = (dz, z, y, gamma, stats, rm, rv, eps, act, slope, p, dy)
+        if sg is not None and sb is not None and not _SIDE["on"]:
+            K.bn_act_dropout_bwd(*args, sg, sb, accumulate=True)
+            return (dy,) + (None,) * 9
+        if sg is not None and sb is not None:
+            # dy needs the sums on this stream; adding them to the sinks is side work like every
+            # other parameter gradient (a one-row column sum of [dgamma | dbeta])
+            ws = K.bn_workspace(M, W, y.device)
+            K.bn_act_dropout_bwd(*args, None, None, ws=ws)
+            sums = ws.view(torch.float32)[:2 * W].view(1, 2 * W)
+            pairs = [(sums, _joined(sg, sb))] if _adjacent(sg, sb) else [(sums[:, :W], sg), (sums[:, W:], sb)]
+            for src, dst in pairs:
+                _param_launch(lambda src=src, dst=dst: K.colsum(src, dst, accumulate=True), ws, small=True,
+                              job=("c", src, dst))
+            return (dy,) + (None,) * 9
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        K.bn_act_dropout_bwd(*args, dgamma, dbeta)
+        return (dy, dgamma, dbeta) + (None,) * 7
+
+
+def bn_act_dropout(y, bn, act, state=None, site=None, row_offset=0):
+    """dropout(act(bn(y))) for a plain ``torch.nn.BatchNorm1d`` ``bn`` (it only holds the parameters
+    and buffers) on y [rows, W], float32 on the device, W % 64 == 0, 64 <= W <= 1024.
+
+    ``bn.training`` selects batch or running statistics as in torch; a training-mode call updates
+    ``running_mean`` / ``running_var`` / ``num_batches_tracked`` on the device, with or without
+    ``torch.no_grad()``.  ``act``: as ``act_dropout``.  ``state`` (a ``DropoutState`` with its ``p``),
+    ``site``, ``row_offset``: the Dropout after the activation, with ``act_dropout``'s mask; without a
+    state (or with p = 0) the result is act(bn(y))."""
+    if not isinstance(bn, torch.nn.BatchNorm1d):
+        raise TypeError(f"bn_act_dropout needs a torch.nn.BatchNorm1d; got {type(bn).__name__}")
+    if not bn.affine:
+        raise NotImplementedError("bn_act_dropout: BatchNorm1d(affine=False) is not implemented")
+    if not bn.track_running_stats:
+        raise NotImplementedError("bn_act_dropout: BatchNorm1d(track_running_stats=False) is not implemented")
+    if bn.momentum is None:
+        raise NotImplementedError("bn_act_dropout: BatchNorm1d(momentum=None) (cumulative average) is not "
+                                  "implemented")
+    code, slope = _act_code(act)
+    p = 0.0
+    if state is not None:
+        from .dropout import check_p
+        if state.p is None or site is None:
+            raise ValueError("bn_act_dropout with a DropoutState needs the state's p and a site")
+        p = check_p(state.p)
+    site = 0 if site is None else int(site)
+    if site < 0 or int(row_offset) < 0:
+        raise ValueError("site and row_offset must be >= 0")
+    W = bn.num_features
+    if y.dim() != 2 or y.dtype != torch.float32 or y.shape[1] != W:
+        raise ValueError(f"bn_act_dropout needs a float32 [rows, {W}] tensor; got {y.dtype} {tuple(y.shape)}")
+    if W % 64 or not 64 <= W <= 1024:
+        raise NotImplementedError(f"bn_act_dropout runs widths 64, 128, ..., 1024; got {W}")
+    if bn.training and y.shape[0] < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(y.shape)}")
+    if y.shape[0] < 1:
+        raise ValueError("bn_act_dropout needs at least one row")
+    if (y.requires_grad or bn.weight.requires_grad) and code == kernels.HipKernels.ACT_NONE and p > 0.0:
+        raise NotImplementedError("bn_act_dropout(act=None) with dropout has no backward (a zero output is "
+                                  "ambiguous there)")
+    _dev_check(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+    return _BnActDropoutFn.apply(y, bn.weight, bn.bias, bn, code, slope, p, state, site, int(row_offset))
+
+
 def _adjacent(a, b):
     """``b`` starts right where ``a`` ends in the SAME storage (two views into FlatAdam's flat
     buffer): the pair is then one [a; b] tensor without a copy.  Two separate allocations that

@@ -676,6 +676,49 @@ int hicgat_dropout_mask(uint8_t *mask, int M, int W, double p, uint64_t seed, co
  * every dropout site of the step, ordered after it, reads the same new count -- also in a replay. */
 int hicgat_dropout_advance(int64_t *counter, hicgat_stream_t stream);
 
+/* ---- BatchNorm1d over the node axis, fused with the activation and Dropout after it (models.py:
+ * 288-298, :852-862: x = dropout(leaky_relu(bn(dense(x))))) ---------------------------------------
+ *   z = dropout(act(gamma * yhat + beta)),  yhat = ((y - mean) - mean_lo) * rstd  per column
+ * of y [M, W] (row stride ldy).  64 <= W <= 1024 and W % 64 == 0 (else HICGAT_EUNSUPPORTED); y / z /
+ * dz / dy 16-B aligned with every ld >= W and a multiple of 4, eps > 0, 0 < momentum <= 1, M >= 2
+ * with batch statistics and M >= 1 with running ones (else HICGAT_EINVAL); all of it checked before
+ * any launch.  No float atomics: every sum runs in one fixed order, so two calls give the same bits.
+ * act / slope / p / seed / step_counter / step_value / site / row_offset: as hicgat_act_dropout_fwd
+ * (the same mask); p = 0 is act(BN(y)).
+ * stats [4, W] = (mean, mean_lo, rstd, rstd_lo): mean + mean_lo is the batch mean and rstd + rstd_lo
+ * is 1 / sqrt(biased variance + eps), each an fp64 value as two floats (the forward uses rstd alone,
+ * the backward both).  The variance is a fixed-order Chan merge (fp64) of per-64-row-chunk (mean, sum
+ * of squared deviations from it, fp64); E[y^2] - E[y]^2 is never formed. */
+size_t hicgat_bn_workspace_bytes(int M, int W);
+/* The statistics of a training forward and its side effects, all on the device (a captured step
+ * replays them): stats as above;  running_mean = (1 - momentum) running_mean + momentum mean;
+ * running_var likewise with the UNBIASED variance;  *num_batches_tracked += 1 (int64).  Each of the
+ * three buffers may be NULL (not updated).  ws: 16-B aligned, hicgat_bn_workspace_bytes(M, W). */
+int hicgat_bn_stats(const float *y, int64_t ldy, int M, int W, double eps, double momentum, float *stats,
+                    float *running_mean, float *running_var, int64_t *num_batches_tracked, void *workspace,
+                    size_t workspace_bytes, hicgat_stream_t stream);
+/* One pass.  stats given: batch statistics (training).  stats NULL: eval mode, mean = running_mean,
+ * rstd = 1 / sqrt(running_var + eps) computed per thread; nothing is updated. */
+int hicgat_bn_act_dropout_fwd(const float *y, int64_t ldy, int M, int W, const float *gamma, const float *beta,
+                              const float *stats, const float *running_mean, const float *running_var, double eps,
+                              int act, float slope, double p, uint64_t seed, const int64_t *step_counter,
+                              int64_t step_value, uint32_t site, int64_t row_offset, float *z, int64_t ldz,
+                              hicgat_stream_t stream);
+/* g = dz * dropout' * act' from the forward's OUTPUT z as in hicgat_act_dropout_bwd (act = none: g =
+ * dz, z unused; act = none with p > 0 is HICGAT_EUNSUPPORTED);  dbeta = sum g,  dgamma = sum g yhat
+ * (one pass + one launch of fixed-order column sums, fp64: with batch statistics the terms of dy
+ * cancel, almost wholly when M = 2);  then one pass
+ *   dy = gamma rstd (g - dbeta / M - yhat dgamma / M)     (stats given; fp64, rounded once)
+ *   dy = g gamma rstd                                     (stats NULL: running statistics).
+ * dgamma / dbeta (both or neither): written, or added to when accumulate != 0.  Either way the sums
+ * [dgamma | dbeta] are left in the first 2 W floats of the workspace (e.g. to be added to a gradient
+ * buffer by a later launch on another stream). */
+int hicgat_bn_act_dropout_bwd(const float *dz, int64_t lddz, const float *z, int64_t ldz, const float *y, int64_t ldy,
+                              int M, int W, const float *gamma, const float *stats, const float *running_mean,
+                              const float *running_var, double eps, int act, float slope, double p, float *dy,
+                              int64_t lddy, float *dgamma, float *dbeta, int accumulate, void *workspace,
+                              size_t workspace_bytes, hicgat_stream_t stream);
+
 /* ---- Spearman / per-step dSCC (a11: scipy.stats.spearmanr of HiC_GAT_generalize_directly.py:242
  * and combined_loss_training.py:135) ---------------------------------------------------------------
  * Exact Spearman correlation with scipy's tie rule (a tie group shares its average rank), by a
