@@ -23,8 +23,8 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
   hicgat.embed.node2vec                       ~ Node2Vec(...).fit(...) at HiC_GAT_generalize_directly.py:150-155
 Compute runs in libhicgat.so (include/hicgat.h); there is no CPU fallback.
 """
-from . import (_lib, align, dist, dropout, embed, graph, graphs, io, kernels, kr, metrics, nn, ops, optim, synth,  # noqa: F401
-               train)
+from . import (_lib, align, dist, dropout, embed, graph, graphs, io, kernels, kr, metrics, nn, ops, optim,  # noqa: F401
+               paramgrads, synth, train)
 from .dropout import DropoutState  # noqa: F401
 from .gat_models import (GATNet, GATNetHeadsChanged3LayersLeakyReLU,  # noqa: F401
                          GATNetHeadsChanged3LayersLeakyReLUv2,

@@ -57,8 +57,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ops, streams
+from . import ops, paramgrads, streams
 from .ops import _ACTS, weight_grad
+from .paramgrads import ColsumJob, WeightGradJob
 from .optim import FlatAdam
 
 TILE = 128
@@ -658,7 +659,7 @@ class ShardedTrainer:
         o, coords_loc, coords = self._tail()
         # ---- backward -----------------------------------------------------------------------
         dout = self.pack[:, :D]
-        with ops.overlapped_param_grads(self.cuda and ops.OVERLAP_DEFAULT, hold_big=False):
+        with ops.overlapped_param_grads(self.cuda and paramgrads.OVERLAP_DEFAULT, hold_big=False):
             coords_loc.backward(self.dcoords[r0:r1])
             self.gbuf[r0:r1].copy_(o.grad)
             K.agg_bwd_rows(r0, r1, self.act, self.gbuf, self.out, bias, self.out2, dout, self.rs)
@@ -675,7 +676,7 @@ class ShardedTrainer:
                 # lin_l's partial dW over all rows (x replicated) on a side stream of its own (lane 2:
                 # beside the tail's dW GEMMs on lane 0, not queued behind them), the GAT parameter
                 # column sums beside it on this stream
-                with ops._side(self.dh, self.x, lane=2):
+                with ops.side_lane(self.dh, self.x, lane=2):
                     if self.cuda:
                         weight_grad(K, self.dh, self.x, out=self.W.grad, accumulate=True)
                     else:
@@ -738,8 +739,9 @@ class ShardedTrainer:
                 # dxa^hd = dout^hd W_hd, both heads in one grouped launch
                 K.gemm_rows_grouped([(self.dout_l[:, hc[hd]], W[hc[hd]], self.dxa[:, hd * F:(hd + 1) * F], None,
                                       None) for hd in (0, 1)], b_kmajor=1, name="gemm_dx")
-            heads = [("w", self.dout_l[:, hd * C:(hd + 1) * C], self.X4[hd, 0], self.W.grad[hd * C:(hd + 1) * C],
-                      None if self.bias is None else self.bias.grad[hd * C:(hd + 1) * C]) for hd in (0, 1)]
+            heads = [WeightGradJob(self.dout_l[:, hd * C:(hd + 1) * C], self.X4[hd, 0], self.W.grad[hd * C:(hd + 1) * C],
+                                   None if self.bias is None else self.bias.grad[hd * C:(hd + 1) * C])
+                     for hd in (0, 1)]
             side = None
             if self.cuda and XAGG_SIDE_BRANCH:
                 side = self.grad_stream
@@ -748,12 +750,13 @@ class ShardedTrainer:
             # rows: tall sums (rows / 2 and rows), taken in the S row segments of gsd -- S x the blocks of
             # one sum per column chunk (profiles/r06b: 51 us at P = 2, 16 at P = 8 as one sum)
             if self.cuda:
-                g_jobs = [("c", self.gpart, self.g_src, False)] + [
-                    ("c", self.x[r0:r1], self.g_dst[:, hd * F:(hd + 1) * F], False, rs_own[:, 3 * H + hd])
-                    for hd in range(H)]
+                g_jobs = [ColsumJob(self.gpart, self.g_src, accumulate=False)] + [
+                    ColsumJob(self.x[r0:r1], self.g_dst[:, hd * F:(hd + 1) * F], accumulate=False,
+                              weights=rs_own[:, 3 * H + hd]) for hd in range(H)]
             else:
-                g_jobs = [("c", self.gpart, self.g_src[0], False),
-                          ("w", rs_own[:, 3 * H:4 * H], self.x[r0:r1], self.g_dst[0].view(H, F), None, False)]
+                g_jobs = [ColsumJob(self.gpart, self.g_src[0], accumulate=False),
+                          WeightGradJob(rs_own[:, 3 * H:4 * H], self.x[r0:r1], self.g_dst[0].view(H, F),
+                                        accumulate=False)]
             # (the side work captured after the edge pass instead -- the edge pass first in the graph's
             # order -- measured slower: 0.485 / 0.491 vs 0.468 / 0.470 ms, profiles/r05l_sim_ab.txt)
             # Buffers on the two branches until the join below.  The side branch reads dout_l, X4[:, 0],
@@ -794,7 +797,7 @@ class ShardedTrainer:
                       self.out, self.out2, self.rs)
         o, coords_loc, coords = self._tail()
         # ---- backward -----------------------------------------------------------------------
-        with ops.overlapped_param_grads(self.cuda and ops.OVERLAP_DEFAULT, hold_big=False):
+        with ops.overlapped_param_grads(self.cuda and paramgrads.OVERLAP_DEFAULT, hold_big=False):
             coords_loc.backward(self.dcoords[self.r0:self.r1])
             dout, rs_all = self.pack[:, :D], self.pack[:, D:]
             self.gbuf[q0:q1].copy_(o.grad)
@@ -813,7 +816,7 @@ class ShardedTrainer:
             with torch.no_grad():
                 # lin_l's dW on the side stream (joined before the gradient all-reduce), param_grad
                 # beside it on this stream
-                with ops._side(self.dh, self.x_loc):
+                with ops.side_lane(self.dh, self.x_loc):
                     if self.cuda:
                         weight_grad(K, self.dh[q0:q1], self.x_loc, out=self.W.grad, accumulate=True)
                     else:

@@ -10,6 +10,7 @@ import os
 import torch
 
 from . import _lib
+from .paramgrads import ColsumJob, WeightGradJob
 
 # name -> list of (start, end) torch.cuda.Event pairs recorded around launches (bench.py)
 TIMERS = None
@@ -432,22 +433,23 @@ class HipKernels:
 
     def param_grads_grouped(self, wjobs, cjobs, target_wgs=None, small_m=None):
         """Every queued parameter gradient of a step in two launches (include/hicgat.h
-        hicgat_param_grads_grouped): ``wjobs`` = [(dy [K, M], x [K, N], dW [M, N], db [M] or None,
-        accumulate)], ``cjobs`` = [(src [rows, cols], dst [cols], accumulate[, wt [rows] view])].
+        hicgat_param_grads_grouped): ``wjobs`` = [paramgrads.WeightGradJob(dy [K, M], x [K, N], dW [M, N],
+        db [M] or None, accumulate)], ``cjobs`` = [paramgrads.ColsumJob(src [rows, cols], dst [cols],
+        accumulate, weights [rows] view or None)] (or plain tuples in the fields' order).
         A weight gradient of fewer than ``SMALL_M`` output rows (dense3: 3, g_dst: 2) becomes M
         weighted column sums (and a plain one for db) instead of a 128 x 128 MFMA tile that would
         be 97 % padding (``small_m``: that bound, default ``SMALL_M``; 0: every job a tile -- the
         tall weighted sums of a 20 000-row step are long single-block chains)."""
         target = self.GROUP_WGS if target_wgs is None else target_wgs
         small_m = self.SMALL_M if small_m is None else small_m
-        big, cjobs = [], list(cjobs)
-        for dy, x, dw, db, acc in wjobs:
-            if dy.shape[1] < small_m:
-                cjobs += [(x, dw[m], acc, dy[:, m]) for m in range(dy.shape[1])]
-                if db is not None:
-                    cjobs.append((dy, db, acc))
+        big, cjobs = [], [ColsumJob(*j) for j in cjobs]
+        for j in (WeightGradJob(*j) for j in wjobs):
+            if j.dy.shape[1] < small_m:
+                cjobs += [ColsumJob(j.x, j.dW[m], j.accumulate, j.dy[:, m]) for m in range(j.dy.shape[1])]
+                if j.db is not None:
+                    cjobs.append(ColsumJob(j.dy, j.db, j.accumulate))
             else:
-                big.append((dy, x, dw, db, acc))
+                big.append(j)
         wjobs = big
         W = (_lib.WgradJob * max(1, len(wjobs)))()
         for k, (dy, x, dw, db, acc) in enumerate(wjobs):
@@ -456,9 +458,7 @@ class HipKernels:
             W[k] = _lib.WgradJob(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dw.data_ptr(), dw.stride(0),
                                  None if db is None else db.data_ptr(), dy.shape[1], x.shape[1], dy.shape[0], int(acc))
         C = (_lib.ColsumJob * max(1, len(cjobs)))()
-        for k, job in enumerate(cjobs):
-            src, dst, acc = job[:3]
-            wt = job[3] if len(job) > 3 else None
+        for k, (src, dst, acc, wt) in enumerate(cjobs):
             assert src.dim() == 2 and src.stride(1) == 1
             if dst.dim() == 2:    # [segs, cols]: the rows summed in segs segments, one dst row each
                 assert dst.stride(1) == 1 and dst.shape[1] == src.shape[1] and 1 <= dst.shape[0] <= max(1, src.shape[0])

@@ -7,11 +7,15 @@
 """
 import contextlib
 import os
-import threading
 
 import torch
 
-from . import _lib, kernels, streams
+from . import _lib, kernels, paramgrads, streams
+# the parameter-gradient scheduler's functions, so callers say ops.overlapped_param_grads() as before
+# (its knobs -- BIG_GROUP, SIDE_GROUPED, ... -- live in paramgrads alone)
+from .paramgrads import (ColsumJob, WeightGradJob, grouped_flush, grouped_param_grads,  # noqa: F401
+                         overlapped_param_grads, param_launch, side_begin, side_flush, side_join, side_lane,
+                         side_mark, side_record)
 
 
 def _sink(p):
@@ -22,248 +26,6 @@ def _sink(p):
     if p is not None and getattr(p, "_hicgat_grad_sink", False) and p.grad is not None:
         return p.grad
     return None
-
-
-# ---- weight-gradient side stream ---------------------------------------------------------------
-# The parameter-gradient kernels (split-K dW GEMMs, bias column sums, GAT param_grad) feed only the
-# optimizer, never the next backward op, so inside ``overlapped_param_grads`` they are issued on a
-# side stream that forks from the backward's stream and is joined back before anything reads the
-# flat gradient buffer (Adam / the gradient all-reduce).  The MFMA-bound GEMMs then run beside the
-# L2-bound aggregation backward instead of in series with it; in a captured step the fork and join
-# are graph edges.  Only sink-bound gradients (``_sink``) go to the side stream -- a gradient that
-# is returned to autograd is consumed on the backward's stream and must be produced there.
-_SIDE = {"on": 0, "streams": {}, "mains": {}, "hold": [], "queue": [], "grouped": 0, "jobs": [], "no_big": 0}
-_SIDE_LOCK = threading.Lock()
-OVERLAP_DEFAULT = True
-# The tail's parameter-gradient launches (split-K dW GEMMs with their bias sums, the LayerNorm
-# dgamma/dbeta sums, bias column sums) are DEFERRED: queued, and issued by ``side_flush`` on the side
-# stream beside the GAT source-side gather (forked after the gather-free row pass).  Issued as they
-# come, a captured step's graph placed some of them in front of the aggregation backward on its
-# queue (2.036 vs 2.060 ms per step).  Measured slower and removed: largest-first
-# or small-first issue order, the big dW GEMMs on a stream of their own or on the backward's stream,
-# lin_l's dW queued behind the side work, the GAT param_grad on a second side stream or split around
-# the gather, the source pass in row chunks, two side lanes on one GPU.
-
-
-# single-GPU step: parameter-gradient jobs of at least this many multiply-adds (the first tail block's
-# 512 x 512 dW, 5.2e9 at N = 20000) are held and issued with lin_l's dW as ONE grouped launch after
-# the source gather (0: off -- they go to the side stream like the rest).  Round 4: 1.876 / 1.879 vs
-# 1.889 / 1.888 ms per step with one side launch per item (profiles/r04i_ab_big_group.txt); with the
-# side work as one grouped launch (SIDE_GROUPED) the big dW rides there: 0 since round 6
-BIG_GROUP = float(os.environ.get("HICGAT_BIG_GROUP", "0"))
-
-
-def side_begin():
-    """Route sink-bound parameter gradients to the side stream until ``side_join``."""
-    with _SIDE_LOCK:
-        _SIDE["on"] += 1
-
-
-def side_mark():
-    """An event on the current stream marking where queued side work may start (``side_flush``)."""
-    if not _SIDE["on"] or not _SIDE["queue"]:
-        return None
-    return streams.record()
-
-
-_FLUSH_LANES = (0, 4, 5, 6)
-SMALL_WORK = 4e6   # side_flush(lanes > 1): items below this many multiply-adds go first in their lane
-# single-GPU step (one lane): the queued side work -- every dW / db / LayerNorm sum of the MLP tail,
-# the first block's 512 x 512 dW included (BIG_GROUP 0) -- as ONE grouped weight-gradient + ONE
-# grouped column-sum launch (hicgat_param_grads_grouped) beside the source gather, when every item has
-# a job descriptor, instead of ~13 launches that each waited for room beside the gather; 0: one
-# launch per item.  SIDE_GROUP_WGS: the grouped launch's workgroup target (the K split): fewer
-# workgroups take fewer CUs from the gather; SIDE_SMALL_M 0: dense3's 3-row dW as an MFMA tile, not
-# three 20 000-row weighted column sums (single-block chains, 157 µs of the side lane).  1.730-1.732
-# vs 1.769-1.771 ms per step (profiles/r06rst_ab_side_grouped.txt, r06u_ab_side_grouped.txt)
-SIDE_GROUPED = os.environ.get("HICGAT_SIDE_GROUPED", "1") != "0"
-SIDE_GROUP_WGS = int(os.environ.get("HICGAT_SIDE_GROUP_WGS", "192"))
-SIDE_SMALL_M = int(os.environ.get("HICGAT_SIDE_SMALL_M", "0"))
-
-
-def side_flush(after=None, lanes=1):
-    """Issue the queued parameter-gradient launches on the side stream, forked from the current
-    stream at this point, or from the earlier point ``after`` (an event from ``side_mark``): the
-    caller can then enqueue its own next kernel first, so a captured graph lists that kernel
-    ahead of the side branch (they read only tensors produced before the fork point).
-
-    ``lanes`` > 1 spreads the launches over that many side streams (largest work first, each to the
-    least-loaded lane; every launch writes its own parameters' gradients, so they are independent):
-    a rank's shard of the multi-GPU slab step has a gather window too short for the tail's queued
-    launches in one chain.  The single-GPU step keeps one lane (a second one measured slower there,
-    DESIGN section 7)."""
-    with _SIDE_LOCK:
-        queue, _SIDE["queue"] = _SIDE["queue"], []
-    if not queue:
-        return
-    n = max(1, min(lanes, len(_FLUSH_LANES)))
-    if n == 1 and SIDE_GROUPED and all(q[3] is not None for q in queue):
-        with _side(*[t for _, keep, _, _ in queue for t in keep], after=after, lane=_FLUSH_LANES[0]):
-            streams.stamp("side_begin")
-            _grouped_launch(kernels.default(), [q[3] for q in queue], SIDE_GROUP_WGS, small_m=SIDE_SMALL_M)
-            streams.stamp("side_end")
-        return
-    load, parts = [0] * n, [[] for _ in range(n)]
-    if n == 1:
-        parts[0] = queue                     # backward order
-    else:
-        for item in sorted(queue, key=lambda q: -q[2]):
-            k = min(range(n), key=lambda a: (load[a], len(parts[a])))
-            parts[k].append(item)
-            load[k] += item[2]
-    for lane, items in zip(_FLUSH_LANES, parts):
-        if n > 1:
-            # reductions without a GEMM (LayerNorm dgamma/dbeta sums: inputs ready, a few us each)
-            # first in their lane, then the GEMMs
-            items = [q for q in items if q[2] < SMALL_WORK] + [q for q in items if q[2] >= SMALL_WORK]
-        if items:
-            with _side(*[t for _, keep, _, _ in items for t in keep], after=after, lane=lane):
-                streams.stamp("side_begin")
-                for fn, _, _, _ in items:
-                    fn()
-                streams.stamp("side_end")
-
-
-def side_record():
-    """Events recorded now on every side stream in use: they complete when the side work issued
-    so far (e.g. the tail's flushed dW GEMMs) has run.  [] when nothing went to a side stream."""
-    if not _SIDE["on"]:
-        return []
-    with _SIDE_LOCK:
-        sides = [_SIDE["streams"][key] for key in _SIDE["mains"]]
-    return [streams.record(st) for st in sides]
-
-
-@contextlib.contextmanager
-def grouped_param_grads():
-    """Inside: the sink-bound parameter gradients that have a job descriptor (every dW / db / LayerNorm
-    sum of the Linear, dual-Linear and fused-tail backward) are collected instead of launched;
-    ``grouped_flush`` then issues ALL of them as two launches (hicgat_param_grads_grouped).  A rank's
-    share of the sharded step is too small for ~15 separate launches: queued over side lanes they
-    were the critical path after the edge pass (profiles/r03w_simprof_xagg_P8_rank0_timeline.txt)."""
-    with _SIDE_LOCK:
-        _SIDE["grouped"] += 1
-    try:
-        yield
-    except BaseException:
-        # a failed backward: drop the collected descriptors, so no later grouped_flush adds this
-        # step's partial dW / db into another step's gradient
-        with _SIDE_LOCK:
-            _SIDE["jobs"].clear()
-        raise
-    finally:
-        with _SIDE_LOCK:
-            _SIDE["grouped"] -= 1
-
-
-def grouped_flush(K=None, extra=(), target_wgs=None, small_m=None):
-    """Issue the collected jobs (plus ``extra`` descriptors) on the current stream: one grouped
-    weight-gradient launch and one grouped column-sum launch.  Returns the tensors they read (the
-    caller keeps them alive until the launches are ordered before any reuse)."""
-    with _SIDE_LOCK:
-        jobs, _SIDE["jobs"] = _SIDE["jobs"], []
-    jobs = jobs + [(j, ()) for j in extra]
-    if not jobs:
-        return []
-    _grouped_launch(K if K is not None else kernels.default(), [j for j, _ in jobs], target_wgs, small_m)
-    return [t for _, keep in jobs for t in keep]
-
-
-def _grouped_launch(K, descs, target_wgs=None, small_m=None):
-    """descriptors: ("w", dy, x, dW, db[, accumulate]) / ("c", src, dst[, accumulate[, row weights]]);
-    accumulate defaults on; a 2-D dst [segs, cols] takes the rows' sum in segments
-    (kernels.param_grads_grouped)"""
-    w = [(j[1], j[2], j[3], j[4], j[5] if len(j) > 5 else True) for j in descs if j[0] == "w"]
-    c = [(j[1], j[2], j[3] if len(j) > 3 else True) + ((j[4],) if len(j) > 4 else ()) for j in descs
-         if j[0] == "c"]
-    K.param_grads_grouped(w, c, target_wgs, small_m)
-
-
-def side_join():
-    """Flush the queue, make every stream that forked work onto the side stream wait for it, and
-    drop the held inputs.  Always runs the queued launches, even after an exception upstream, so
-    no gradient kernel is left behind for a later step."""
-    try:
-        side_flush()
-        if _SIDE["jobs"] and not _SIDE["grouped"]:
-            # held big jobs that no GATConv backward issued (BIG_GROUP with another model): now
-            _SIDE["hold"].extend(grouped_flush())
-    finally:
-        with _SIDE_LOCK:
-            _SIDE["on"] = max(0, _SIDE["on"] - 1)
-            for key, main in _SIDE["mains"].items():
-                streams.join(main, _SIDE["streams"][key])
-            _SIDE["mains"].clear()
-            _SIDE["hold"].clear()
-
-
-@contextlib.contextmanager
-def overlapped_param_grads(enabled=None, hold_big=True):
-    """``with overlapped_param_grads(): loss.backward()`` -- parameter gradients overlap the rest
-    of the backward and are complete (ordered before the caller's stream) on exit.
-
-    ``hold_big=False``: no BIG_GROUP holding -- for a backward that has no ``_GATConvFn`` to issue
-    the held jobs with lin_l's dW (the sharded step runs the GATConv backward itself; a held job
-    would otherwise be issued by ``side_join`` on the main stream, after the caller recorded the
-    side streams' completion for its gradient all-reduce)."""
-    if not (OVERLAP_DEFAULT if enabled is None else enabled):
-        yield
-        return
-    side_begin()
-    if not hold_big:
-        with _SIDE_LOCK:
-            _SIDE["no_big"] += 1
-    try:
-        yield
-    finally:
-        try:
-            side_join()
-        finally:
-            if not hold_big:
-                with _SIDE_LOCK:
-                    _SIDE["no_big"] -= 1
-
-
-def _param_launch(fn, *keep, small=False, work=0, job=None):
-    """Launch a sink-bound parameter-gradient kernel ``fn()``: now on the current stream when not
-    overlapping; queued for ``side_flush`` when deferring (``work``: its size, the issue order);
-    else now on the side stream.  ``keep`` are the tensors ``fn`` reads (held until the join).
-    ``job``: the same work as a descriptor for ``grouped_flush`` -- ("w", dy, x, dW, db) for
-    dW += dy^T x (and db += column sums of dy), ("c", src, dst) for dst += column sums of src."""
-    if job is not None and (_SIDE["grouped"] or (BIG_GROUP > 0 and _SIDE["on"] and not _SIDE["no_big"]
-                                                 and work >= BIG_GROUP)):
-        with _SIDE_LOCK:
-            _SIDE["jobs"].append((job, keep))
-        return
-    if not _SIDE["on"]:
-        fn()
-    else:
-        with _SIDE_LOCK:
-            _SIDE["queue"].append((fn, keep, work, job))
-
-
-def _side(*keep, after=None, lane=0):
-    """Stream context for a sink-bound gradient kernel: side stream ``lane`` (after a fork from the
-    current stream, or from the event ``after``) while overlapping, else a no-op.  ``keep`` are
-    the inputs the side kernels read; they stay referenced until the join so the caching
-    allocator cannot hand their memory to a later backward kernel while the side stream still
-    reads it."""
-    if not _SIDE["on"]:
-        return contextlib.nullcontext()
-    cur = torch.cuda.current_stream()
-    dev = cur.device
-    key = (dev, lane)
-    with _SIDE_LOCK:
-        side = _SIDE["streams"].get(key)
-        if side is None:
-            side = _SIDE["streams"][key] = streams.get(f"side{lane}", dev)
-        _SIDE["mains"].setdefault(key, cur)
-        _SIDE["hold"].extend(keep)
-    if after is not None:
-        streams.wait(side, after)
-    else:
-        streams.fork(side, cur)
-    return torch.cuda.stream(side)
 
 
 def _dev_check(*ts):
@@ -373,10 +135,8 @@ class _GATConvFn(torch.autograd.Function):
         dW = None
         if ctx.needs_input_grad[1]:
             gW = _sink(pW)
-            if gW is not None and _SIDE["jobs"]:
-                # the held big dW jobs and lin_l's as one grouped launch (BIG_GROUP)
-                _SIDE["hold"].extend(grouped_flush(K, [("w", dh, x, gW, None)]))
-            else:
+            # the held big dW jobs and lin_l's as one grouped launch (BIG_GROUP), else lin_l's alone
+            if gW is None or not paramgrads.flush_held(K, [WeightGradJob(dh, x, gW)]):
                 dW = weight_grad(K, dh, x, out=gW, accumulate=gW is not None)
                 if gW is not None:
                     dW = None
@@ -417,8 +177,8 @@ def _weight_grad_to(K, p, dy, x):
     """dW = dy^T x into the parameter's sink (returns None) or a new tensor (returned)."""
     g = _sink(p)
     if g is not None:
-        _param_launch(lambda: weight_grad(K, dy, x, out=g, accumulate=True), dy, x,
-                      work=dy.shape[0] * dy.shape[1] * x.shape[1], job=("w", dy, x, g, None))
+        param_launch(lambda: weight_grad(K, dy, x, out=g, accumulate=True), dy, x,
+                     work=dy.shape[0] * dy.shape[1] * x.shape[1], job=WeightGradJob(dy, x, g))
         return None
     return weight_grad(K, dy, x)
 
@@ -431,17 +191,15 @@ def _wb_grad_to(K, pW, pb, dy, x, need_w=True, need_b=True):
     mixed."""
     need_b = need_b and pb is not None
     if not need_w:
-        dW = _weight_grad_to(K, pW, dy, x) if need_w else None
-        db = _bias_grad_to(K, pb, dy) if need_b else None
-        return dW, db
+        return None, (_bias_grad_to(K, pb, dy) if need_b else None)
     gW = _sink(pW)
     gb = _sink(pb) if need_b else None
     rows, m = dy.shape
     n = x.shape[1]
     sp = _splits(m, n, rows)
     if gW is not None and (gb is not None or not need_b):
-        _param_launch(lambda: K.wgrad(dy, x, gW, gb, accumulate=True, splits=sp), dy, x, work=rows * m * n,
-                      job=("w", dy, x, gW, gb))
+        param_launch(lambda: K.wgrad(dy, x, gW, gb, accumulate=True, splits=sp), dy, x, work=rows * m * n,
+                     job=WeightGradJob(dy, x, gW, gb))
         return None, None
     if gW is None and (not need_b or _sink(pb) is None):
         dW = torch.empty((m, n), dtype=torch.float32, device=dy.device)
@@ -455,7 +213,7 @@ def _bias_grad_to(K, p, dy):
     """db = column sums of dy into the parameter's sink (returns None) or a new tensor."""
     g = _sink(p)
     if g is not None:
-        _param_launch(lambda: K.colsum(dy, g, accumulate=True), dy, small=True, job=("c", dy, g))
+        param_launch(lambda: K.colsum(dy, g, accumulate=True), dy, job=ColsumJob(dy, g))
         return None
     return K.colsum(dy, torch.empty(dy.shape[1], dtype=torch.float32, device=dy.device))
 
@@ -636,20 +394,28 @@ class _LnReluResFn(torch.autograd.Function):
         y, stats, gamma, beta = ctx.saved_tensors
         dz = dz.contiguous()
         dy = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-        sg, sb = _sink(ctx.params[0]), _sink(ctx.params[1])
-        if sg is not None and sb is not None and not _SIDE["on"]:
-            K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, sg, sb, accumulate=True)
-            dgamma = dbeta = None
-        elif sg is not None and sb is not None:
-            ws = K.ln_workspace(y.shape[1], y.device)
-            K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, None, None, ws=ws)
-            _param_launch(lambda: K.ln_relu_res_bwd_params(y.shape[1], sg, sb, ws, accumulate=True), ws)
-            dgamma = dbeta = None
-        else:
-            dgamma = torch.empty_like(gamma)
-            dbeta = torch.empty_like(beta)
-            K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, dgamma, dbeta)
+        dgamma, dbeta = _ln_bwd(K, *ctx.params, dz, y, stats, gamma, beta, dy)
         return dy, dgamma, dbeta, (dz if ctx.has_res else None), None
+
+
+def _ln_bwd(K, pg, pb, dz, y, stats, gamma, beta, dy, **dres):
+    """The LayerNorm backward's row pass (dy, and ``dres=``) with its dgamma / dbeta sums, which go:
+    without both sinks into new tensors (returned); with them and nothing overlapping straight into
+    the sinks; while overlapping into a workspace as partials, and adding those to the sinks is
+    queued side work (it has no grouped form).  Returns (dgamma, dbeta) for autograd."""
+    sg, sb = _sink(pg), _sink(pb)
+    if sg is None or sb is None:
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+        K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, dgamma, dbeta, **dres)
+        return dgamma, dbeta
+    if not paramgrads.overlapping():
+        K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, sg, sb, accumulate=True, **dres)
+    else:
+        W = y.shape[1]
+        ws = K.ln_workspace(W, y.device)
+        K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, None, None, ws=ws, **dres)
+        param_launch(lambda: K.ln_relu_res_bwd_params(W, sg, sb, ws, accumulate=True), ws)
+    return None, None
 
 
 def ln_relu_res(y, norm, res=None):
@@ -703,7 +469,7 @@ class _BnActDropoutFn(torch.autograd.Function):
         dy = torch.empty((M, W), dtype=torch.float32, device=y.device)
         sg, sb = _sink(ctx.params[0]), _sink(ctx.params[1])
         args = (dz, z, y, gamma, stats, rm, rv, eps, act, slope, p, dy)
-        if sg is not None and sb is not None and not _SIDE["on"]:
+        if sg is not None and sb is not None and not paramgrads.overlapping():
             K.bn_act_dropout_bwd(*args, sg, sb, accumulate=True)
             return (dy,) + (None,) * 9
         if sg is not None and sb is not None:
@@ -714,8 +480,8 @@ class _BnActDropoutFn(torch.autograd.Function):
             sums = ws.view(torch.float32)[:2 * W].view(1, 2 * W)
             pairs = [(sums, _joined(sg, sb))] if _adjacent(sg, sb) else [(sums[:, :W], sg), (sums[:, W:], sb)]
             for src, dst in pairs:
-                _param_launch(lambda src=src, dst=dst: K.colsum(src, dst, accumulate=True), ws, small=True,
-                              job=("c", src, dst))
+                param_launch(lambda src=src, dst=dst: K.colsum(src, dst, accumulate=True), ws,
+                             job=ColsumJob(src, dst))
             return (dy,) + (None,) * 9
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
         K.bn_act_dropout_bwd(*args, dgamma, dbeta)
@@ -814,17 +580,7 @@ class _DualLnReluResFn(torch.autograd.Function):
         dz = dz.contiguous()
         M, w = dz.shape
         dY = torch.empty((M, 2 * w), dtype=torch.float32, device=dz.device)
-        sg, sb = _sink(pg), _sink(pb)
-        dgamma = dbeta = None
-        if sg is not None and sb is not None and not _SIDE["on"]:
-            K.ln_relu_res_bwd(dz, Y[:, :w], stats, gamma, beta, dY[:, :w], sg, sb, accumulate=True, dres=dY[:, w:])
-        elif sg is not None and sb is not None:
-            ws = K.ln_workspace(w, dz.device)
-            K.ln_relu_res_bwd(dz, Y[:, :w], stats, gamma, beta, dY[:, :w], None, None, dres=dY[:, w:], ws=ws)
-            _param_launch(lambda: K.ln_relu_res_bwd_params(w, sg, sb, ws, accumulate=True), ws)
-        else:
-            dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-            K.ln_relu_res_bwd(dz, Y[:, :w], stats, gamma, beta, dY[:, :w], dgamma, dbeta, dres=dY[:, w:])
+        dgamma, dbeta = _ln_bwd(K, pg, pb, dz, Y[:, :w], stats, gamma, beta, dY[:, :w], dres=dY[:, w:])
         dx = None
         if ctx.needs_input_grad[0]:
             dx = K.gemm(0, 1, M, x.shape[1], 2 * w, dY, _joined(W1, W2).contiguous(), torch.empty_like(x),
@@ -844,19 +600,19 @@ def _dual_param_grads(K, W1, b1, W2, b2, dY, x):
     if w_pair and b_pair:
         # [dW1; dW2] and [db1; db2] of the pair in ONE GEMM launch (hicgat_gemm_wgrad)
         gWj, gbj, sp = _joined(sW1, sW2), _joined(sb1, sb2), _splits(2 * w, x.shape[1], M)
-        _param_launch(lambda: K.wgrad(dY, x, gWj, gbj, accumulate=True, splits=sp), dY, x,
-                      work=M * 2 * w * x.shape[1], job=("w", dY, x, gWj, gbj))
+        param_launch(lambda: K.wgrad(dY, x, gWj, gbj, accumulate=True, splits=sp), dY, x,
+                     work=M * 2 * w * x.shape[1], job=WeightGradJob(dY, x, gWj, gbj))
     else:
         if w_pair:
             gWj = _joined(sW1, sW2)
-            _param_launch(lambda: weight_grad(K, dY, x, out=gWj, accumulate=True), dY, x,
-                          job=("w", dY, x, gWj, None))
+            param_launch(lambda: weight_grad(K, dY, x, out=gWj, accumulate=True), dY, x,
+                         job=WeightGradJob(dY, x, gWj))
         else:
             dW1 = _weight_grad_to(K, W1, dY[:, :w], x)
             dW2 = _weight_grad_to(K, W2, dY[:, w:], x)
         if b_pair:
             gbj = _joined(sb1, sb2)
-            _param_launch(lambda: K.colsum(dY, gbj, accumulate=True), dY, small=True, job=("c", dY, gbj))
+            param_launch(lambda: K.colsum(dY, gbj, accumulate=True), dY, job=ColsumJob(dY, gbj))
         else:
             db1 = _bias_grad_to(K, b1, dY[:, :w].contiguous())
             db2 = _bias_grad_to(K, b2, dY[:, w:].contiguous())
@@ -873,7 +629,7 @@ def _ln_param_grads(K, gamma, beta, ws, rows):
     sg, sb = _sink(gamma), _sink(beta)
     if sg is not None and sb is not None and _adjacent(sg, sb):
         gj = _joined(sg, sb)
-        _param_launch(lambda: K.colsum(part, gj, accumulate=True), ws, work=rows * 2 * W, job=("c", part, gj))
+        param_launch(lambda: K.colsum(part, gj, accumulate=True), ws, work=rows * 2 * W, job=ColsumJob(part, gj))
         return None, None
     out = K.colsum(part, torch.empty(2 * W, dtype=torch.float32, device=part.device))
     return out[:W], out[W:]

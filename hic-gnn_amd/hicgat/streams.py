@@ -4,7 +4,7 @@ Streams.  ``get(name, device)`` is THE stream of that name on that device: made 
 by libhicgat (``hicgat_stream_create``: a non-blocking HIP stream) and wrapped as a
 ``torch.cuda.ExternalStream``; it lives as long as the process.  Names in use: "capture" (the
 origin stream of every ``graphs.CapturedStep``), "warm" (its eager warm-up), "side0", "side2",
-"side4", "side5", "side6" (``ops``' parameter-gradient lanes), "comm" (the slab / allgather forms'
+"side4", "side5", "side6" (``paramgrads``' parameter-gradient lanes), "comm" (the slab / allgather forms'
 tail gradient bucket) and "grad" (the xagg form's side branch).  Until round 5 every trainer,
 ``CapturedStep`` and lane asked torch for a new stream; torch hands out its pool of 32 streams
 round robin, so after a few trainers in one process two "different" lanes of a step, or a lane and
@@ -29,7 +29,7 @@ a later capture).
 Rule 2 is the pattern the round-5 slab step had when its captures aborted (a ``capture_end``
 segfault and a core dump, both in the slab form with the simulated communicator; DESIGN.md section
 6, "Streams and capture"): it recorded events on the side lanes after their parameter-gradient
-launches, joined the lanes back (``ops.side_join``), and only then made the comm stream wait on
+launches, joined the lanes back (``paramgrads.side_join``), and only then made the comm stream wait on
 those events before its gradient all-reduce.  The bare pattern alone did not fault in a standalone
 probe (tools/capture_probe.py); the streams of the same runs also aliased through torch's pool (see
 above).  Both are gone, and the ledger keeps the step inside the fork / join forms that are known
@@ -76,6 +76,16 @@ def get(name, device=None):
                 s = torch.cuda.ExternalStream(h.value, device=dev)
                 _STREAMS[key] = s
     return s
+
+
+def current():
+    """The current stream.  ``paramgrads`` asks here (and ``use``), so a host test can stand in for both."""
+    return torch.cuda.current_stream()
+
+
+def use(stream):
+    """Context: ``stream`` is the current stream inside."""
+    return torch.cuda.stream(stream)
 
 
 def made():
@@ -132,7 +142,7 @@ def end_capture():
 
 def record(stream=None):
     """An event recorded now on ``stream`` (default: the current stream), tagged for the ledger."""
-    s = torch.cuda.current_stream() if stream is None else stream
+    s = current() if stream is None else stream
     ev = torch.cuda.Event()
     ev.record(s)
     L = LEDGER

@@ -287,14 +287,16 @@ class CpuKernels:
             row_stats[r0:r1, 3 * H:4 * H] = (q - row_stats[r0:r1, 2 * H:3 * H].double() * s3).float()
 
     def param_grads_grouped(self, wjobs, cjobs, target_wgs=None, small_m=None):
-        for dy, x, dw, db, acc in wjobs:
-            r = dy.double().t() @ x.double()
-            dw.copy_((r + dw.double()).float() if acc else r.float())
-            if db is not None:
-                b = dy.double().sum(0)
-                db.copy_((b + db.double()).float() if acc else b.float())
-        for src, dst, acc in cjobs:
-            self.colsum(src, dst, accumulate=acc)
+        """``wjobs`` / ``cjobs``: paramgrads.WeightGradJob / ColsumJob records (no row weights here)."""
+        for j in wjobs:
+            r = j.dy.double().t() @ j.x.double()
+            j.dW.copy_((r + j.dW.double()).float() if j.accumulate else r.float())
+            if j.db is not None:
+                b = j.dy.double().sum(0)
+                j.db.copy_((b + j.db.double()).float() if j.accumulate else b.float())
+        for j in cjobs:
+            assert j.weights is None
+            self.colsum(j.src, j.dst, accumulate=j.accumulate)
 
     def xagg_slab_sum(self, rowptr_s, perm, ds, x, da_src, g_src):
         N = da_src.shape[0]

@@ -186,7 +186,7 @@ def _worker(rank, world, port, backend, n, out, mode="slab", big_group=None):
     try:
         hicgat, adj, truth, x = _inputs(n, dev)
         if big_group is not None:
-            hicgat.ops.BIG_GROUP = big_group
+            hicgat.paramgrads.BIG_GROUP = big_group
         torch.manual_seed(0)
         model = hicgat.GATNetSelectiveResidualsUpdated().to(dev)
         tr = hicgat.dist.ShardedTrainer(model, x, adj, truth, lr=1e-3, mode=mode)
@@ -226,7 +226,7 @@ def test_sharded_single_rank_rccl_equals_autograd_step(tmp_path, mode, n, big):
     differently, so a relu input at rounding level from 0 may flip; those entries are masked and
     everything else must hold loss to the north star's 1e-5 and gradients to 1e-4 of their max.
     n = 777 is the size whose block-2 LN output at |z| = 6e-8 flipped in round 3; n = 20000 is the
-    synth-20000 workload (BASELINE configs[2]).  ``big`` = 1: ops.BIG_GROUP lowered so that EVERY
+    synth-20000 workload (BASELINE configs[2]).  ``big`` = 1: paramgrads.BIG_GROUP lowered so that EVERY
     parameter-gradient job of the MLP tail qualifies for holding -- the sharded step must not hold
     them (it has no GATConv backward to issue them before its gradient all-reduce's tail bucket)."""
     res = _run(1, "nccl", n, tmp_path, mode, big)

@@ -795,7 +795,7 @@ def test_overlapped_param_grads_same_bits(monkeypatch):
     K split) the eager and captured steps are bit-equal to each other and within fp32 reassociation
     of the serial backward."""
     import hicgat
-    from hicgat import ops, synth
+    from hicgat import paramgrads, synth
     n = 1200
     i, j, c = synth.contact_pairs(n, density=0.05, seed=2)
     A = synth.dense_contacts(n, i, j, c, device=DEV)
@@ -804,9 +804,9 @@ def test_overlapped_param_grads_same_bits(monkeypatch):
     x = torch.tensor(synth.features(n, seed=2), device=DEV)
 
     def run(overlap, graphed, grouped, steps=4):
-        monkeypatch.setattr(ops, "OVERLAP_DEFAULT", overlap)
-        monkeypatch.setattr(ops, "SIDE_GROUPED", grouped)
-        monkeypatch.setattr(ops, "BIG_GROUP", 0.0 if grouped else 5e9)
+        monkeypatch.setattr(paramgrads, "OVERLAP_DEFAULT", overlap)
+        monkeypatch.setattr(paramgrads, "SIDE_GROUPED", grouped)
+        monkeypatch.setattr(paramgrads, "BIG_GROUP", 0.0 if grouped else 5e9)
         torch.manual_seed(0)
         model = hicgat.GATNetSelectiveResidualsUpdated().to(DEV)
         opt = hicgat.FlatAdam(model.flat_parameters(), lr=1e-3)

@@ -48,9 +48,9 @@ def main():
         K0 = tr.K
         orig = K0.param_grads_grouped
 
-        def spy(w, c, target=None):
+        def spy(w, c, target=None, small_m=None):
             rec.append((list(w), list(c), target))
-            return orig(w, c, target)
+            return orig(w, c, target, small_m)
         K0.param_grads_grouped = spy
         tr.opt.enable_device_step()
         tr.step()
@@ -91,10 +91,10 @@ def main():
         if c and w:
             res[f"{pre} column-sum jobs only"] = timeit(lambda: Kp.param_grads_grouped([], c, tg))
         for k, job in enumerate(c):
-            res[f"{pre} colsum job {k} {tuple(job[0].shape)}{' weighted' if len(job) > 3 else ''}"] = \
+            res[f"{pre} colsum job {k} {tuple(job.src.shape)}{' weighted' if job.weights is not None else ''}"] = \
                 timeit(lambda job=job: Kp.param_grads_grouped([], [job], tg))
         for k, job in enumerate(w):
-            res[f"{pre} wgrad job {k} dy {tuple(job[0].shape)} x {tuple(job[1].shape)}"] = \
+            res[f"{pre} wgrad job {k} dy {tuple(job.dy.shape)} x {tuple(job.x.shape)}"] = \
                 timeit(lambda job=job: Kp.param_grads_grouped([job], [], tg))
     print(f"rank {a.rank} of {a.world}: rows {tr.local_rows}, nnz {tr.local_nnz}, dxa finite "
           f"{bool(torch.isfinite(tr.dxa).all())}, |dxa| max {float(tr.dxa.abs().max()):.3e}, "
