@@ -12,6 +12,8 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
                                               ~ models.py:60-98 / :971-1007 / :1365-1411 / :1461-1494
   hicgat.gat_models.GATNetHeadsChanged4LayersLeakyReLU / GATNetHeadsChanged4LayersLeakyReLUHeads4
       (BatchNorm1d + feature dropout)         ~ models.py:270-319 / :834-883
+  hicgat.gat_models.GATNetHeadsChanged3LayersEmbeddingDim256Entropy (attention weights + entropy term)
+                                              ~ models.py:1112-1148
   hicgat.ops.bn_act_dropout                   ~ torch.nn.BatchNorm1d -> F.leaky_relu -> torch.nn.Dropout(p)
   hicgat.ops.act_dropout, hicgat.DropoutState ~ x.relu() / F.leaky_relu(x) -> torch.nn.Dropout(p)
   hicgat.graph.load_input / cont2dist / convert_to_matrix / Adj
@@ -26,7 +28,8 @@ Compute runs in libhicgat.so (include/hicgat.h); there is no CPU fallback.
 from . import (_lib, align, dist, dropout, embed, graph, graphs, io, kernels, kr, metrics, nn, ops, optim,  # noqa: F401
                paramgrads, synth, train)
 from .dropout import DropoutState  # noqa: F401
-from .gat_models import (GATNet, GATNetHeadsChanged3LayersLeakyReLU,  # noqa: F401
+from .gat_models import (GATNet, GATNetHeadsChanged3LayersEmbeddingDim256Entropy,  # noqa: F401
+                         GATNetHeadsChanged3LayersLeakyReLU,
                          GATNetHeadsChanged3LayersLeakyReLUv2,
                          GATNetHeadsChanged4LayerEmbedding512Dense,
                          GATNetHeadsChanged4LayersLeakyReLU,

@@ -73,6 +73,11 @@ SIGNATURES = {
     "hicgat_gat_param_grad": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_int, c_p,
                                       c_sz, c_p]),
     "hicgat_gat_param_grad_workspace_bytes": (c_sz, [c_int, c_int]),
+    "hicgat_gat_transpose_map": (c_int, [c_p, c_p, c_int, c_p, c_p]),
+    "hicgat_gat_alpha": (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_f, c_p, c_p]),
+    "hicgat_gat_alpha_bwd_dst": (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
+    "hicgat_gat_alpha_bwd_src": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                         c_f, c_p, c_p, c_p, c_p]),
     "hicgat_pairdist_fwd": (c_int, [c_p, c_int, c_p, c_i64, c_p]),
     "hicgat_pairdist_bwd": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p, c_sz, c_p]),
     "hicgat_pairdist_mse_fused": (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_p,

@@ -23,6 +23,12 @@ Two more that also normalise with ``torch.nn.BatchNorm1d`` over the node rows (`
                                                   tune_hyperparams_embeddings.py:48 scores.
 * ``GATNetHeadsChanged4LayersLeakyReLUHeads4`` -- models.py:834-883, GATConv(256, 256, heads=4) (569 859).
 
+One that returns its attention weights and trains with an attention-entropy term through them
+(``GATConv(..., return_attention_weights=True)``, gat_attn.hip):
+
+* ``GATNetHeadsChanged3LayersEmbeddingDim256Entropy`` -- models.py:1112-1148, GATConv(256, 128, heads=2)
+                                                         (107 651 parameters); 256 feature columns.
+
 As in the reference, ``get_model`` never drops and ``forward`` / ``loss`` drop iff ``self.training``.
 The masks are not torch's: they are a counter-based function of (seed, step, site, row, column)
 (DESIGN.md "Feature dropout"), so a captured step replays them.  ``GATNetReduced`` still refuses to
@@ -155,6 +161,56 @@ class GATNetHeadsChangedLeakyReLU(_CoordsModel):
 
     def get_model(self, x, edge_index):
         return self.tail(self.conv(x, edge_index))
+
+
+class GATNetHeadsChanged3LayersEmbeddingDim256Entropy(_CoordsModel):
+    """models.py:1112-1148: GATConv(256, 128, heads=2) called with ``return_attention_weights=True`` ->
+    relu -> 256-128-64-3 with relu between (107 651 parameters); 256 feature columns.  ``forward`` returns
+    ``(D, attn)`` like the reference (``attn``: see ``GATConv.forward``), ``get_model`` the coordinates.
+
+    The reference carries ``self.alpha = 0.01`` for an attention-entropy term, but no script of it trains
+    this model, so the objective is this project's: ``loss()`` returns
+
+        fused_dist_loss(coords, truth, kind) + self.alpha * attention_entropy(alpha) / (N * H)
+
+    -- the mean entropy per (row, head) of the attention distributions, weighted by ``self.alpha``
+    (``ops.attention_entropy``).  Its gradient reaches the GATConv through the attention weights."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(256, 128, heads=2, concat=True)
+        self.densea = Linear(256, 128)
+        self.dense1 = Linear(128, 64)
+        self.dense2 = Linear(64, 3)
+        self.alpha = 0.01
+
+    conv_act = "relu"   # the relu after the GATConv runs in the aggregation's epilogue
+
+    def post_act(self, x):
+        x = F.relu(_lin(self.densea, x))
+        x = F.relu(_lin(self.dense1, x))
+        return _lin(self.dense2, x)
+
+    def tail(self, x):
+        return self.post_act(F.relu(x))
+
+    def coords_and_attention(self, x, edge_index):
+        x, attn = self.conv(x, edge_index, act=self.conv_act, return_attention_weights=True)
+        return self.post_act(x), attn
+
+    def get_model(self, x, edge_index):
+        return self.coords_and_attention(x, edge_index)[0]
+
+    def forward(self, x, edge_index):
+        coords, attn = self.coords_and_attention(x, edge_index)
+        return ops.pairwise_dist(coords), attn
+
+    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None):
+        coords, attn = self.coords_and_attention(x, edge_index)
+        loss, stats = ops.fused_dist_loss(coords, truth, kind, tile_range, stats)
+        w = attn.storage.value()
+        loss = loss + (self.alpha / (x.shape[0] * w.shape[1])) * ops.attention_entropy(w)
+        return loss, stats, coords
 
 
 class GATNetReduced(_CoordsModel):
@@ -433,4 +489,5 @@ MODELS = {
     "GATNetMoreReduced": GATNetMoreReduced,
     "GATNetHeadsChanged4LayersLeakyReLU": GATNetHeadsChanged4LayersLeakyReLU,
     "GATNetHeadsChanged4LayersLeakyReLUHeads4": GATNetHeadsChanged4LayersLeakyReLUHeads4,
+    "GATNetHeadsChanged3LayersEmbeddingDim256Entropy": GATNetHeadsChanged3LayersEmbeddingDim256Entropy,
 }

@@ -175,6 +175,37 @@ class Adj:
         return obj
 
 
+    def transpose_map(self):
+        """``tmap32`` [nnz] int32 over the device CSR: the index of edge (i, r) for edge (r, i)
+        (hicgat_gat_transpose_map), which the backward of the attention weights reads.  Built once per
+        CSR and cached; a CSR that is not structurally symmetric is refused here (one host read)."""
+        key = (self.rowptr32.data_ptr(), self.col32.data_ptr())
+        cache = getattr(self, "_tmap", None)
+        if cache is None or cache[0] != key:
+            from . import kernels
+            t = kernels.default().transpose_map(self.rowptr32, self.col32)
+            if t.numel() and int(t.min()) < 0:
+                raise ValueError("the adjacency is not structurally symmetric: some edge (r, i) has no (i, r)")
+            self._tmap = cache = (key, t)
+        return cache[1]
+
+    @property
+    def tmap32(self):
+        return self.transpose_map()
+
+    def with_self_loops(self, value):
+        """An ``Adj`` over the self-looped device CSR (PyG's ``set_diag``'d SparseTensor) carrying
+        ``value`` [nnz, ...] per entry: what ``GATConv(..., return_attention_weights=True)`` returns.
+        Its ``storage`` is int64 on the CSR's device (converted once per CSR and cached here); it shares
+        this one's int32 device arrays."""
+        key = (self.rowptr32.data_ptr(), self.col32.data_ptr())
+        cache = getattr(self, "_csr64", None)
+        if cache is None or cache[0] != key:
+            self._csr64 = cache = (key, self.rowptr32.long(), self.col32.long())
+        out = Adj(_csr=(cache[1], cache[2], value, self.n))
+        out.rowptr32, out.col32 = self.rowptr32, self.col32
+        return out
+
     def tiles(self, min_edges=None):
         """The dense-tile split of the device CSR (``build_tiles``), built once per CSR and cached;
         None when tiling is off (HICGAT_TILE_MIN=0) or, for the default threshold, when the dense

@@ -210,6 +210,47 @@ class HipKernels:
                                                       _lib.stream(dev)), "hicgat_gat_param_grad")
         return datt_l, datt_r, dbias
 
+    # -- the attention weights and their backward (gat_attn.hip) ----------------------------------------
+    def transpose_map(self, rowptr, col):
+        """tmap [nnz] int32: the CSR index of the transposed edge (-1 where it is missing)."""
+        N = rowptr.numel() - 1
+        tmap = torch.empty(col.numel(), dtype=torch.int32, device=col.device)
+        _lib.check(self.lib.hicgat_gat_transpose_map(P(rowptr), P(col), N, P(tmap), _lib.stream(col.device)),
+                   "hicgat_gat_transpose_map")
+        return tmap
+
+    def gat_alpha(self, rowptr, col, C, a_src, a_dst, row_stats, ns, alpha):
+        """alpha [nnz, H] of the aggregation whose row statistics are in ``row_stats``."""
+        N, H = a_src.shape
+        assert alpha.shape == (col.numel(), H) and alpha.is_contiguous() and row_stats.stride(0) == 4 * H
+        with _timed("gat_alpha"):
+            _lib.check(self.lib.hicgat_gat_alpha(P(rowptr), P(col), N, H, C, P(a_src), P(a_dst), P(row_stats),
+                                                 float(ns), P(alpha), _lib.stream(alpha.device)), "hicgat_gat_alpha")
+        return alpha
+
+    def gat_alpha_bwd_dst(self, rowptr, col, C, a_src, a_dst, alpha, G, ns, c, da_dst_g):
+        """Row pass of dL/dalpha = ``G`` [nnz, H]: c and da_dst^G, both [N, H] (written)."""
+        N, H = a_src.shape
+        assert G.shape == alpha.shape and G.is_contiguous() and alpha.is_contiguous()
+        assert c.shape == (N, H) and da_dst_g.shape == (N, H) and c.is_contiguous() and da_dst_g.is_contiguous()
+        with _timed("gat_alpha_bwd_dst"):
+            _lib.check(self.lib.hicgat_gat_alpha_bwd_dst(P(rowptr), P(col), N, H, C, P(a_src), P(a_dst), P(alpha),
+                                                         P(G), float(ns), P(c), P(da_dst_g),
+                                                         _lib.stream(alpha.device)), "hicgat_gat_alpha_bwd_dst")
+
+    def gat_alpha_bwd_src(self, rowptr, col, tmap, a_src, a_dst, alpha, G, c, da_dst_g, att_l, att_r, ns, dh, da_src,
+                          row_stats):
+        """Source pass of ``G``: adds its share onto dh, da_src and row_stats' da_dst slot in place."""
+        N, H = a_src.shape
+        C = dh.shape[1] // H
+        assert tmap.numel() == col.numel() and G.is_contiguous() and alpha.is_contiguous()
+        assert dh.is_contiguous() and da_src.is_contiguous() and row_stats.stride(0) == 4 * H
+        with _timed("gat_alpha_bwd_src"):
+            _lib.check(self.lib.hicgat_gat_alpha_bwd_src(P(rowptr), P(col), P(tmap), N, H, C, P(a_src), P(a_dst),
+                                                         P(alpha), P(G), P(c), P(da_dst_g), P(att_l), P(att_r),
+                                                         float(ns), P(dh), P(da_src), P(row_stats),
+                                                         _lib.stream(alpha.device)), "hicgat_gat_alpha_bwd_src")
+
     # -- aggregate-first GATConv (gat_xagg.hip): the multi-GPU "xagg" step (hicgat.dist) ---------------
     def xagg_logits(self, x, W, att_l, att_r, a_src, a_dst, zero=None, step_ctr=None, pack=None):
         """a_src / a_dst [N, 2] = x . (W_h^T att^h) for every row of x; ``zero``: a contiguous buffer

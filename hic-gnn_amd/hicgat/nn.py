@@ -56,11 +56,19 @@ class GATConv(torch.nn.Module):
             with torch.no_grad():
                 self.bias.zero_()
 
-    def forward(self, x, edge_index, act=None):
+    def forward(self, x, edge_index, act=None, return_attention_weights=None):
         """``edge_index`` is a ``hicgat.graph.Adj`` (the reference passes a SparseTensor).
-        ``act="relu"`` (not in PyG) returns relu(forward(x)) with the relu fused into the kernel."""
-        return ops.gat_conv(x, self.lin_l.weight, self.att_l, self.att_r, self.bias, edge_index,
-                            self.negative_slope, act)
+        ``act="relu"`` (not in PyG) returns relu(forward(x)) with the relu fused into the kernel.
+        ``return_attention_weights=True`` returns ``(out, attn)`` as PyG does for a SparseTensor input
+        (``edge_index.set_value(alpha, layout='coo')``): ``attn`` is an ``Adj`` over the self-looped CSR
+        whose ``storage.rowptr()`` / ``col()`` are int64 and whose ``storage.value()`` is alpha [nnz, H],
+        attached to autograd (a loss may depend on it)."""
+        if not return_attention_weights:
+            return ops.gat_conv(x, self.lin_l.weight, self.att_l, self.att_r, self.bias, edge_index,
+                                self.negative_slope, act)
+        out, alpha = ops.gat_conv(x, self.lin_l.weight, self.att_l, self.att_r, self.bias, edge_index,
+                                  self.negative_slope, act, return_attention_weights=True)
+        return out, edge_index.with_self_loops(alpha)
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"

@@ -49,7 +49,8 @@ class _GATConvFn(torch.autograd.Function):
     is a streaming pass (``agg_bwd_rows``) and only the source half gathers."""
 
     @staticmethod
-    def forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, tiles=None):
+    def forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, tiles=None, tmap=None):
+        # tmap: only from _GATConvAttnFn, which runs this body and then adds the attention weights
         _lib.lib()
         _dev_check(x, W, att_l, att_r, bias, rowptr, col)
         K = kernels.default()
@@ -85,12 +86,19 @@ class _GATConvFn(torch.autograd.Function):
         ctx.ns = float(negative_slope)
         ctx.act = act
         ctx.params = (W, att_l, att_r, bias)
+        if tmap is not None:
+            alpha = torch.empty((col.numel(), H), dtype=torch.float32, device=x.device)
+            K.gat_alpha(rowptr, col, D // H, a_src, a_dst, row_stats, negative_slope, alpha)
+            if train:
+                ctx.save_for_backward(x, W, al, ar, h, a_src, a_dst, row_stats, rowptr, col, out, out2, b, alpha, tmap)
+            return out, alpha
         return out
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, G=None):
+        # G: only from _GATConvAttnFn, dL/dalpha [nnz, H]; its share is added after the source pass
         K = kernels.default()
-        x, W, al, ar, h, a_src, a_dst, row_stats, rowptr, col, out, out2, b = ctx.saved_tensors
+        x, W, al, ar, h, a_src, a_dst, row_stats, rowptr, col, out, out2, b = ctx.saved_tensors[:13]
         N = x.shape[0]
         H = al.shape[-2]
         fused = ctx.rows_state is not None and ctx.rows_state["dout"] is not None
@@ -121,6 +129,14 @@ class _GATConvFn(torch.autograd.Function):
             K.agg_bwd_src(rowptr, col, 0, N, h, a_src, a_dst, row_stats, dout, al, ar, ctx.ns, dh, da_src)
             streams.stamp("src_end")
         side_flush(after=fork)
+        if G is not None:
+            # the backward is linear in (dout, G): G's share adds onto dh, da_src and row_stats' da_dst
+            # slot, and the parameter gradients, lin_l's dW and dx below see the totals
+            alpha, tmap = ctx.saved_tensors[13:]
+            c, dd = torch.empty_like(a_src), torch.empty_like(a_src)
+            K.gat_alpha_bwd_dst(rowptr, col, h.shape[1] // H, a_src, a_dst, alpha, G, ctx.ns, c, dd)
+            K.gat_alpha_bwd_src(rowptr, col, tmap, a_src, a_dst, alpha, G, c, dd, al, ar, ctx.ns, dh, da_src,
+                                row_stats)
         # after the gathers: the GAT column sums, then lin_l's dW on this stream (with the held
         # first-block dW: BIG_GROUP).  The column sums on a side stream beside the grouped dW launch:
         # 1.964 / 1.970 vs 1.877 / 1.872 ms per step (profiles/r04l_ab_single_gpu.txt)
@@ -144,6 +160,34 @@ class _GATConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = K.gemm(0, 1, N, x.shape[1], h.shape[1], dh, W, torch.empty_like(x), name="gemm_dx")
         return (dx, dW, datt_l, datt_r, dbias, None, None, None, None, None)
+
+
+class _GATConvAttnFn(torch.autograd.Function):
+    """``_GATConvFn`` that also returns the attention weights alpha [nnz, H] (self-looped CSR order;
+    PyG's ``return_attention_weights=True``) as a second differentiable output.  The forward is
+    ``_GATConvFn``'s plus one pass that writes alpha from the row statistics (gat_attn.hip).  The
+    backward takes (dout, dalpha): without a dalpha it is ``_GATConvFn.backward`` launch for launch;
+    with one, two more passes add its share after the source pass; a missing dout counts as zeros."""
+
+    @staticmethod
+    def forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, tiles, tmap):
+        ctx.set_materialize_grads(False)    # an unused output's gradient arrives as None, not as zeros
+        return _GATConvFn.forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, tiles, tmap)
+
+    @staticmethod
+    def backward(ctx, dout, dalpha):
+        if dout is None:
+            if dalpha is None:
+                return (None,) * 11
+            dout = torch.zeros_like(ctx.saved_tensors[10])
+        G = None if dalpha is None else dalpha.contiguous().float()
+        return _GATConvFn.backward(ctx, dout, G) + (None,)
+
+
+def attention_entropy(alpha):
+    """-sum(alpha * log(alpha + 1e-12)) over every (edge, head) of the attention weights, in plain torch
+    ops (the eps of the reference's ``entropy_of_predictions``, HiC_GAT_generalize_directly.py:54-58)."""
+    return -(alpha * torch.log(alpha + 1e-12)).sum()
 
 
 # target workgroups of a split-K weight-gradient GEMM.  Alone, 512 measured best at N = 20000 (0.094
@@ -840,8 +884,10 @@ def gat_shape_supported(H, C):
     return 1 <= H <= 4 and C > 0 and C % 128 == 0 and (H * C) % 256 == 0 and H * C <= 1024
 
 
-def gat_conv(x, W, att_l, att_r, bias, adj, negative_slope=0.2, act=None):
-    """GATConv forward; ``act="relu"`` returns relu(GATConv(x)) with the relu fused."""
+def gat_conv(x, W, att_l, att_r, bias, adj, negative_slope=0.2, act=None, return_attention_weights=False):
+    """GATConv forward; ``act="relu"`` returns relu(GATConv(x)) with the relu fused.
+    ``return_attention_weights=True`` returns ``(out, alpha)``: alpha [nnz, H] in the order of the
+    self-looped device CSR (``adj.rowptr32`` / ``adj.col32``), attached to autograd."""
     H, C = att_l.shape[-2], att_l.shape[-1]
     if not gat_shape_supported(H, C):
         raise NotImplementedError(f"GATConv(heads={H}, out_channels={C}) is not supported by the aggregation "
@@ -850,6 +896,9 @@ def gat_conv(x, W, att_l, att_r, bias, adj, negative_slope=0.2, act=None):
         adj.to(x.device)
     # the matrix-core tiled form (gat_tiles.hip) is (2, 256) only: every other shape gathers
     tiles = adj.tiles() if (H, C) == (2, 256) else None
+    if return_attention_weights:
+        return _GATConvAttnFn.apply(x, W, att_l, att_r, bias, adj.rowptr32, adj.col32, negative_slope, _ACTS[act],
+                                    tiles, adj.transpose_map())
     return _GATConvFn.apply(x, W, att_l, att_r, bias, adj.rowptr32, adj.col32, negative_slope, _ACTS[act], tiles)
 
 

@@ -149,6 +149,37 @@ int hicgat_gat_agg_bwd_src_ex(const int32_t *rowptr, const int32_t *col, int N, 
                               const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
                               const float *att_src, const float *att_dst, float neg_slope, float *dh, float *da_src,
                               int flags, hicgat_stream_t stream);
+/* ---- the attention weights as an output, and their backward (gat_attn.hip) ---------------------
+ * Reference: PyG 1.7.2 GATConv.forward(x, edge_index, return_attention_weights=True), which
+ * models.py:1122 calls: alpha [nnz, H] in the order of the self-looped CSR, an autograd tensor there.
+ * Same CSR, a_src / a_dst [N, H] and row_stats [N, 4H] as the aggregation above, same supported
+ * (H, C) set (other shapes: HICGAT_EUNSUPPORTED).  One wave per row, no atomics, fixed summation order.
+ *   hicgat_gat_transpose_map: tmap[e(r, i)] = e(i, r) over the CSR (a binary search per edge in row
+ *     i's sorted columns); its own inverse, the identity on the self loops; -1 where (i, r) is
+ *     missing (the CSR is not structurally symmetric).  Built once per graph.
+ *   hicgat_gat_alpha: alpha[e, h] = exp(lrelu(a_src[j] + a_dst[i]) - max_i) / (sum_i + 1e-16) from
+ *     row_stats[i, 0..2H) (after hicgat_gat_agg_fwd*); gathers no h rows.
+ * For G = dL/dalpha [nnz, H], with s = lrelu'(a_src[j] + a_dst[i]):
+ *   hicgat_gat_alpha_bwd_dst, row i: c[i, h] = sum_j alpha_ij G_ij and
+ *     da_dst_g[i, h] = sum_j alpha_ij s_ij (G_ij - c[i, h])            (both [N, H], written).
+ *   hicgat_gat_alpha_bwd_src, row r: ds = sum_e alpha[t] s (G[t] - c[col[e]]), t = tmap[e], then IN
+ *     PLACE dh[r] += ds (x) att_src + da_dst_g[r] (x) att_dst, da_src[r] += ds,
+ *     row_stats[r, 3H..4H) += da_dst_g[r].  Runs after hicgat_gat_agg_bwd_src (or its tiled form) and
+ *     before hicgat_gat_param_grad, which then sees the totals.
+ * The two backward passes read alpha as hicgat_gat_alpha wrote it. */
+int hicgat_gat_transpose_map(const int32_t *rowptr, const int32_t *col, int N, int32_t *tmap,
+                             hicgat_stream_t stream);
+int hicgat_gat_alpha(const int32_t *rowptr, const int32_t *col, int N, int H, int C, const float *a_src,
+                     const float *a_dst, const float *row_stats, float neg_slope, float *alpha,
+                     hicgat_stream_t stream);
+int hicgat_gat_alpha_bwd_dst(const int32_t *rowptr, const int32_t *col, int N, int H, int C, const float *a_src,
+                             const float *a_dst, const float *alpha, const float *G, float neg_slope, float *c,
+                             float *da_dst_g, hicgat_stream_t stream);
+int hicgat_gat_alpha_bwd_src(const int32_t *rowptr, const int32_t *col, const int32_t *tmap, int N, int H, int C,
+                             const float *a_src, const float *a_dst, const float *alpha, const float *G,
+                             const float *c, const float *da_dst_g, const float *att_src, const float *att_dst,
+                             float neg_slope, float *dh, float *da_src, float *row_stats, hicgat_stream_t stream);
+
 /* ---- GATConv in aggregate-first order (gat_xagg.hip; the multi-GPU "xagg" step of hicgat.dist) ----
  * Reference: the same PyG 1.7.2 GATConv (models.py:619) -- out_i^h = W_h (sum_j alpha_ij^h x_j) +
  * b^h and a_src_j^h = <W_h^T att_src^h, x_j> are the h-first expressions regrouped, so a rank that
