@@ -102,10 +102,10 @@ extern "C" int hicgat_adam_step(float *param, const float *grad, float *exp_avg,
   return HICGAT_OK;
 }
 
-extern "C" int hicgat_adam_step_table_ex(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
-                                         int64_t n, double beta1, double beta2, double eps, const float *table,
-                                         int64_t table_len, int64_t *step_counter, int counted,
-                                         hicgat_stream_t stream) {
+extern "C" int hicgat_adam_step_table(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
+                                      int64_t n, double beta1, double beta2, double eps, const float *table,
+                                      int64_t table_len, int64_t *step_counter, int counted,
+                                      hicgat_stream_t stream) {
   if (n < 0 || table_len < 1 || (counted != 0 && counted != 1)) return HICGAT_EINVAL;
   if (!param || !grad || !exp_avg || !exp_avg_sq || !table || !step_counter) return HICGAT_EINVAL;
   const uintptr_t mis = reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
@@ -130,13 +130,6 @@ extern "C" int hicgat_adam_step_table_ex(float *param, const float *grad, float 
     HICGAT_CHECK_LAUNCH();
   }
   return HICGAT_OK;
-}
-
-extern "C" int hicgat_adam_step_table(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
-                                      int64_t n, double beta1, double beta2, double eps, const float *table,
-                                      int64_t table_len, int64_t *step_counter, hicgat_stream_t stream) {
-  return hicgat_adam_step_table_ex(param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, table, table_len,
-                                   step_counter, 0, stream);
 }
 
 extern "C" int hicgat_step_begin(float *grad, int64_t n, int64_t *step_counter, hicgat_stream_t stream) {

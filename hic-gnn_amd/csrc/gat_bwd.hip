@@ -207,15 +207,15 @@ extern "C" int hicgat_gat_agg_bwd_dst(const int32_t *rowptr, const int32_t *col,
   return HICGAT_OK;
 }
 
-// The one implementation of the source pass's three entry points.  HICGAT_SRC_ROUND_ROBIN turns the
-// XCD remap off; the occupancy cap goes with the remapped (whole-graph) pass at (2, 256) only.
-extern "C" int hicgat_gat_agg_bwd_src_ex(const int32_t *rowptr, const int32_t *col, int N, int H,
-                                         int C, int row_begin, int row_end, const float *h,
-                                         const float *a_src, const float *a_dst,
-                                         const float *row_stats, int64_t ld_stats, const float *dout,
-                                         int64_t ld_dout, const float *att_src, const float *att_dst,
-                                         float neg_slope, float *dh, float *da_src, int flags,
-                                         hicgat_stream_t stream) {
+// HICGAT_SRC_ROUND_ROBIN turns the XCD remap off; the occupancy cap goes with the remapped
+// (whole-graph) pass at (2, 256) only.
+extern "C" int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H,
+                                      int C, int row_begin, int row_end, const float *h,
+                                      const float *a_src, const float *a_dst,
+                                      const float *row_stats, int64_t ld_stats, const float *dout,
+                                      int64_t ld_dout, const float *att_src, const float *att_dst,
+                                      float neg_slope, float *dh, float *da_src, int flags,
+                                      hicgat_stream_t stream) {
   if (flags & ~HICGAT_SRC_ROUND_ROBIN) return HICGAT_EINVAL;
   const bool remap = !(flags & HICGAT_SRC_ROUND_ROBIN);
   if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
@@ -240,29 +240,6 @@ extern "C" int hicgat_gat_agg_bwd_src_ex(const int32_t *rowptr, const int32_t *c
                        att_dst, neg_slope, dh, da_src);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
-}
-
-extern "C" int hicgat_gat_agg_bwd_src_ld(const int32_t *rowptr, const int32_t *col, int N, int H,
-                                         int C, int row_begin, int row_end, const float *h,
-                                         const float *a_src, const float *a_dst,
-                                         const float *row_stats, int64_t ld_stats, const float *dout,
-                                         int64_t ld_dout, const float *att_src, const float *att_dst,
-                                         float neg_slope, float *dh, float *da_src,
-                                         hicgat_stream_t stream) {
-  return hicgat_gat_agg_bwd_src_ex(rowptr, col, N, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats,
-                                   dout, ld_dout, att_src, att_dst, neg_slope, dh, da_src, 0, stream);
-}
-
-extern "C" int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H,
-                                      int C, int row_begin, int row_end, const float *h,
-                                      const float *a_src, const float *a_dst,
-                                      const float *row_stats, const float *dout,
-                                      const float *att_src, const float *att_dst,
-                                      float neg_slope, float *dh, float *da_src,
-                                      hicgat_stream_t stream) {
-  return hicgat_gat_agg_bwd_src_ex(rowptr, col, N, H, C, row_begin, row_end, h, a_src, a_dst, row_stats,
-                                   4 * (int64_t)H, dout, (int64_t)H * C, att_src, att_dst, neg_slope, dh, da_src, 0,
-                                   stream);
 }
 
 extern "C" int hicgat_gat_agg_bwd_rows(int N, int H, int C, int row_begin, int row_end, int act,

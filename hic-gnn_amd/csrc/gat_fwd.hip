@@ -98,11 +98,11 @@ extern "C" int hicgat_gat_att_logits(const float *h, const float *att_src, const
 // 2 per CU: +30 us), profiles/r05at_gather_occupancy_ab.txt
 constexpr size_t kAggFwdOccLds = 53248;
 
-extern "C" int hicgat_gat_agg_fwd_act(const int32_t *rowptr, const int32_t *col, int N, int nnz,
-                                      int H, int C, int row_begin, int row_end, const float *h,
-                                      const float *a_src, const float *a_dst, const float *bias,
-                                      float neg_slope, int act, float *out, float *out2,
-                                      float *row_stats, hicgat_stream_t stream) {
+extern "C" int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz,
+                                  int H, int C, int row_begin, int row_end, const float *h,
+                                  const float *a_src, const float *a_dst, const float *bias,
+                                  float neg_slope, int act, float *out, float *out2,
+                                  float *row_stats, hicgat_stream_t stream) {
   if (N < 0 || nnz < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
   if (act != 0 && act != 1) return HICGAT_EINVAL;
   if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
@@ -127,13 +127,4 @@ extern "C" int hicgat_gat_agg_fwd_act(const int32_t *rowptr, const int32_t *col,
 #undef HICGAT_FWD_LAUNCH
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
-}
-
-extern "C" int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H,
-                                  int C, int row_begin, int row_end, const float *h,
-                                  const float *a_src, const float *a_dst, const float *bias,
-                                  float neg_slope, float *out, float *row_stats,
-                                  hicgat_stream_t stream) {
-  return hicgat_gat_agg_fwd_act(rowptr, col, N, nnz, H, C, row_begin, row_end, h, a_src, a_dst, bias,
-                                neg_slope, 0, out, nullptr, row_stats, stream);
 }

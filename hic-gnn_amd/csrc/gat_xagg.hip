@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void xagg_vec_kernel(const float *__restrict__
                                                        int64_t *__restrict__ step_ctr, const PackJobs pj) {
   __shared__ float red[4][64];
   // the optimizer's device step count advances here, at the step's first launch (Adam reads it at
-  // the step's end: hicgat_adam_step_table_ex with counted = 1, no increment launch of its own)
+  // the step's end: hicgat_adam_step_table with counted = 1, no increment launch of its own)
   if (step_ctr && blockIdx.x == 0 && threadIdx.x == 0) step_ctr[0] = step_ctr[0] + 1;
   if (zero_buf) {   // the step's flat gradient buffer (zero_grad) rides along: float4 stores, then the tail
     const int64_t n4 = zero_n / 4, stride = (int64_t)gridDim.x * 256;
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void xagg_vec_kernel(const float *__restrict__
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) reinterpret_cast<float4 *>(zero_buf)[i] = z;
     for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < zero_n; i += stride) zero_buf[i] = 0.f;
   }
-  // blocks 32.. (hicgat_xagg_logits_zero_pack): the one-kernel tail's packed weights of this step
+  // blocks 32.. (hicgat_xagg_logits with pack): the one-kernel tail's packed weights of this step
   // (pack.hpp; hicgat_tail_pack's launch folded into the step's first one)
   if (blockIdx.x >= 32) {
     pack_block(pj, blockIdx.x - 32);
@@ -681,11 +681,10 @@ using namespace hicgat;
 
 extern "C" size_t hicgat_xagg_vec_bytes(void) { return 4 * 512 * sizeof(float); }
 
-extern "C" int hicgat_xagg_logits_zero_pack(const float *x, const float *W, const float *att_src,
-                                            const float *att_dst, int N, int F, int H, int C, float *vec,
-                                            float *a_src, float *a_dst, float *zero_buf, int64_t zero_n,
-                                            int64_t *step_counter, const float *W1c, const float *W2c, void *pack,
-                                            size_t pack_bytes, hicgat_stream_t stream) {
+extern "C" int hicgat_xagg_logits(const float *x, const float *W, const float *att_src, const float *att_dst, int N,
+                                  int F, int H, int C, float *vec, float *a_src, float *a_dst, float *zero_buf,
+                                  int64_t zero_n, int64_t *step_counter, const float *W1c, const float *W2c,
+                                  void *pack, size_t pack_bytes, hicgat_stream_t stream) {
   if (N < 0 || zero_n < 0) return HICGAT_EINVAL;
   if (F != 512 || H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
   if (!W || !att_src || !att_dst || !vec || (zero_n > 0 && !zero_buf)) return HICGAT_EINVAL;
@@ -706,20 +705,6 @@ extern "C" int hicgat_xagg_logits_zero_pack(const float *x, const float *W, cons
   hipLaunchKernelGGL(xagg_logits_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x, vec, N, a_src, a_dst);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
-}
-
-extern "C" int hicgat_xagg_logits_zero(const float *x, const float *W, const float *att_src, const float *att_dst,
-                                       int N, int F, int H, int C, float *vec, float *a_src, float *a_dst,
-                                       float *zero_buf, int64_t zero_n, int64_t *step_counter,
-                                       hicgat_stream_t stream) {
-  return hicgat_xagg_logits_zero_pack(x, W, att_src, att_dst, N, F, H, C, vec, a_src, a_dst, zero_buf, zero_n,
-                                      step_counter, nullptr, nullptr, nullptr, 0, stream);
-}
-
-extern "C" int hicgat_xagg_logits(const float *x, const float *W, const float *att_src, const float *att_dst, int N,
-                                  int F, int H, int C, float *vec, float *a_src, float *a_dst,
-                                  hicgat_stream_t stream) {
-  return hicgat_xagg_logits_zero(x, W, att_src, att_dst, N, F, H, C, vec, a_src, a_dst, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int hicgat_xagg_fwd(const int32_t *rowptr, const int32_t *col, int N, int F, int H, int C, int row_begin,
@@ -812,21 +797,10 @@ extern "C" int hicgat_xagg_slab_sum(const int32_t *rowptr_s, const int32_t *perm
   return HICGAT_OK;
 }
 
-extern "C" int hicgat_xagg_param_finish(const float *W, const float *att_src, const float *att_dst, const float *g_src,
-                                        const float *g_dst, int F, int H, int C, float *dW, float *datt_src,
-                                        float *datt_dst, hicgat_stream_t stream) {
-  if (F != 512 || H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
-  if (!W || !att_src || !att_dst || !g_src || !g_dst || !dW || !datt_src || !datt_dst) return HICGAT_EINVAL;
-  hipLaunchKernelGGL(xagg_param_finish_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, W, att_src, att_dst,
-                     g_src, g_dst, dW, datt_src, datt_dst, 1, (int64_t)0);
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
-}
-
-extern "C" int hicgat_xagg_param_finish_seg(const float *W, const float *att_src, const float *att_dst,
-                                            const float *g_src, const float *g_dst, int segs, int64_t seg_stride,
-                                            int F, int H, int C, float *dW, float *datt_src, float *datt_dst,
-                                            hicgat_stream_t stream) {
+extern "C" int hicgat_xagg_param_finish(const float *W, const float *att_src, const float *att_dst,
+                                        const float *g_src, const float *g_dst, int segs, int64_t seg_stride,
+                                        int F, int H, int C, float *dW, float *datt_src, float *datt_dst,
+                                        hicgat_stream_t stream) {
   if (F != 512 || H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
   if (!W || !att_src || !att_dst || !g_src || !g_dst || !dW || !datt_src || !datt_dst) return HICGAT_EINVAL;
   if (segs < 1 || (segs > 1 && seg_stride < 1024)) return HICGAT_EINVAL;

@@ -714,16 +714,9 @@ extern "C" size_t hicgat_gemm_workspace_bytes(int M, int N, int splits) {
 }
 
 extern "C" int hicgat_gemm(int a_kmajor, int b_kmajor, int M, int N, int K, const float *A, int64_t lda,
-                           const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
-                           int splits, void *workspace, size_t workspace_bytes, hicgat_stream_t stream) {
-  return hicgat_gemm_ex(a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, bias, C, ldc, accumulate, splits,
-                        HICGAT_GEMM_AUTO, workspace, workspace_bytes, stream);
-}
-
-extern "C" int hicgat_gemm_ex(int a_kmajor, int b_kmajor, int M, int N, int K, const float *A, int64_t lda,
-                              const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc,
-                              int accumulate, int splits, int impl, void *workspace, size_t workspace_bytes,
-                              hicgat_stream_t stream) {
+                           const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc,
+                           int accumulate, int splits, int impl, void *workspace, size_t workspace_bytes,
+                           hicgat_stream_t stream) {
   if (impl == HICGAT_GEMM_X3) return HICGAT_EUNSUPPORTED;   // the bf16 x3 split was measured slower and removed
   if (impl != HICGAT_GEMM_AUTO && impl != HICGAT_GEMM_F32) return HICGAT_EINVAL;
   if (M < 0 || N < 0 || K < 0 || splits < 1) return HICGAT_EINVAL;
@@ -754,7 +747,7 @@ extern "C" int hicgat_gemm_wgrad(int M, int N, int K, const float *dY, int64_t l
     return HICGAT_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   float *slab = static_cast<float *>(workspace);
-  // the dispatch of hicgat_gemm_ex's fp32 path for the (K-major, K-major) layout
+  // the dispatch of hicgat_gemm's fp32 path for the (K-major, K-major) layout
   if (M >= 128 && N >= 128 && M <= 1024)
     return launch<128, 128, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
   if (N >= 128) return launch<64, 128, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);

@@ -884,11 +884,11 @@ extern "C" int hicgat_pairdist_bwd(const float *coords, const float *G, int N, i
   return HICGAT_OK;
 }
 
-extern "C" int hicgat_pairdist_mse_fused_band(const float *coords, const float *T, int N, int64_t ldt,
-                                              int64_t t_row0, int64_t t_rows, int64_t t_col0,
-                                              int64_t tile_begin, int64_t tile_end, int loss_kind,
-                                              double *stats, float *loss, float *dcoords, void *workspace,
-                                              size_t workspace_bytes, hicgat_stream_t stream) {
+extern "C" int hicgat_pairdist_mse_fused(const float *coords, const float *T, int N, int64_t ldt,
+                                         int64_t t_row0, int64_t t_rows, int64_t t_col0,
+                                         int64_t tile_begin, int64_t tile_end, int loss_kind,
+                                         double *stats, float *loss, float *dcoords, void *workspace,
+                                         size_t workspace_bytes, hicgat_stream_t stream) {
   if (N < 0 || loss_kind < KIND_MSE || loss_kind > KIND_CONTRASTIVE) return HICGAT_EINVAL;
   if (N == 0) return HICGAT_OK;
   if (!coords || !T || !stats || !workspace) return HICGAT_EINVAL;
@@ -946,16 +946,6 @@ extern "C" int hicgat_pairdist_mse_fused_band(const float *coords, const float *
   return HICGAT_OK;
 }
 
-extern "C" int hicgat_pairdist_mse_fused(const float *coords, const float *T, int N, int64_t ldt,
-                                         int64_t tile_begin, int64_t tile_end, int loss_kind,
-                                         double *stats, float *loss, float *dcoords,
-                                         void *workspace, size_t workspace_bytes,
-                                         hicgat_stream_t stream) {
-  if (ldt < N) return HICGAT_EINVAL;
-  return hicgat_pairdist_mse_fused_band(coords, T, N, ldt, 0, N, 0, tile_begin, tile_end, loss_kind, stats, loss,
-                                        dcoords, workspace, workspace_bytes, stream);
-}
-
 extern "C" int hicgat_pairdist_finalize(int N, int loss_kind, double *stats, float *loss,
                                         hicgat_stream_t stream) {
   if (N <= 0 || !stats || loss_kind < KIND_MSE || loss_kind > KIND_CONTRASTIVE) return HICGAT_EINVAL;
@@ -983,9 +973,9 @@ __global__ __launch_bounds__(256) void finalize_rows_kernel(int N, int loss_kind
   }
 }
 
-extern "C" int hicgat_pairdist_finalize_rows_ex(int N, int loss_kind, double *stats, float *loss, const double *dc64,
-                                                int row_begin, int row_end, float *dcoords, const float *cbuf,
-                                                const int32_t *gidx, float *cglob, hicgat_stream_t stream) {
+extern "C" int hicgat_pairdist_finalize_rows(int N, int loss_kind, double *stats, float *loss, const double *dc64,
+                                             int row_begin, int row_end, float *dcoords, const float *cbuf,
+                                             const int32_t *gidx, float *cglob, hicgat_stream_t stream) {
   if (N <= 0 || !stats || loss_kind < KIND_MSE || loss_kind > KIND_CONTRASTIVE) return HICGAT_EINVAL;
   if (row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
   const int64_t n3 = 3 * (int64_t)(row_end - row_begin);
@@ -1000,12 +990,6 @@ extern "C" int hicgat_pairdist_finalize_rows_ex(int N, int loss_kind, double *st
   return HICGAT_OK;
 }
 
-extern "C" int hicgat_pairdist_finalize_rows(int N, int loss_kind, double *stats, float *loss, const double *dc64,
-                                             int row_begin, int row_end, float *dcoords, hicgat_stream_t stream) {
-  return hicgat_pairdist_finalize_rows_ex(N, loss_kind, stats, loss, dc64, row_begin, row_end, dcoords, nullptr,
-                                          nullptr, nullptr, stream);
-}
-
 // ---- background form: T = bg except at a sorted symmetric CSR support + the diagonal -----------
 static int64_t pd_support_blocks(int N) { return (N + 3) / 4; }
 
@@ -1016,13 +1000,12 @@ extern "C" size_t hicgat_pairdist_support_workspace_bytes(int N) {
          kMomBlocks * 8 * sizeof(double) + 2 * (size_t)N * sizeof(float4) + 256;   // corr + the float4 coords
 }
 
-extern "C" int hicgat_pairdist_mse_fused_support_range_ex(const float *coords, const int32_t *cmap, int N,
-                                                          float background, const int32_t *rowptr, const int32_t *col,
-                                                          const float *val, const float *diag, int64_t tile_begin,
-                                                          int64_t tile_end, int support_row_begin, int support_row_end,
-                                                          int loss_kind, double *stats, float *loss, float *dcoords,
-                                                          double *dcoords64, void *workspace,
-                                                          size_t workspace_bytes, hicgat_stream_t stream) {
+extern "C" int hicgat_pairdist_mse_fused_support(const float *coords, const int32_t *cmap, int N, float background,
+                                                 const int32_t *rowptr, const int32_t *col, const float *val,
+                                                 const float *diag, int64_t tile_begin, int64_t tile_end,
+                                                 int support_row_begin, int support_row_end, int loss_kind,
+                                                 double *stats, float *loss, float *dcoords, double *dcoords64,
+                                                 void *workspace, size_t workspace_bytes, hicgat_stream_t stream) {
   if (N < 0 || loss_kind < KIND_MSE || loss_kind > KIND_CONTRASTIVE) return HICGAT_EINVAL;
   if (N == 0) return HICGAT_OK;
   if (!coords || !rowptr || !col || !val || !diag || !stats || !workspace) return HICGAT_EINVAL;
@@ -1100,26 +1083,4 @@ extern "C" int hicgat_pairdist_mse_fused_support_range_ex(const float *coords, c
     HICGAT_CHECK_LAUNCH();
   }
   return HICGAT_OK;
-}
-
-extern "C" int hicgat_pairdist_mse_fused_support_range(const float *coords, int N, float background,
-                                                       const int32_t *rowptr, const int32_t *col, const float *val,
-                                                       const float *diag, int64_t tile_begin, int64_t tile_end,
-                                                       int support_row_begin, int support_row_end, int loss_kind,
-                                                       double *stats, float *loss, float *dcoords, double *dcoords64,
-                                                       void *workspace, size_t workspace_bytes,
-                                                       hicgat_stream_t stream) {
-  return hicgat_pairdist_mse_fused_support_range_ex(coords, nullptr, N, background, rowptr, col, val, diag, tile_begin,
-                                                    tile_end, support_row_begin, support_row_end, loss_kind, stats,
-                                                    loss, dcoords, dcoords64, workspace, workspace_bytes, stream);
-}
-
-extern "C" int hicgat_pairdist_mse_fused_support(const float *coords, int N, float background,
-                                                 const int32_t *rowptr, const int32_t *col, const float *val,
-                                                 const float *diag, int loss_kind, double *stats, float *loss,
-                                                 float *dcoords, void *workspace, size_t workspace_bytes,
-                                                 hicgat_stream_t stream) {
-  return hicgat_pairdist_mse_fused_support_range(coords, N, background, rowptr, col, val, diag, 0, -1, 0, N,
-                                                 loss_kind, stats, loss, dcoords, nullptr, workspace, workspace_bytes,
-                                                 stream);
 }

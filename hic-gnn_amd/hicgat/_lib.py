@@ -50,19 +50,13 @@ SIGNATURES = {
     "hicgat_gat_linear_att": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
     "hicgat_gat_att_logits": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
     "hicgat_gat_agg_fwd": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p,
-                                   c_p, c_f, c_p, c_p, c_p]),
-    "hicgat_gat_agg_fwd_act": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p,
-                                       c_p, c_f, c_int, c_p, c_p, c_p, c_p]),
+                                   c_p, c_f, c_int, c_p, c_p, c_p, c_p]),
     "hicgat_gat_agg_bwd_dst": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
                                        c_f, c_p, c_p]),
     "hicgat_gat_agg_bwd_rows": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p,
                                         c_i64, c_p, c_p]),
-    "hicgat_gat_agg_bwd_src_ld": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
-                                          c_i64, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_p]),
-    "hicgat_gat_agg_bwd_src_ex": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
-                                          c_i64, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_int, c_p]),
     "hicgat_gat_agg_bwd_src": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
-                                       c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
+                                       c_i64, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_int, c_p]),
     "hicgat_gat_agg_fwd_tiled": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int,
                                          c_int, c_p, c_p, c_p, c_p, c_f, c_int, c_p, c_p, c_p, c_int, c_p, c_sz,
                                          c_p]),
@@ -80,24 +74,18 @@ SIGNATURES = {
                                          c_f, c_p, c_p, c_p, c_p]),
     "hicgat_pairdist_fwd": (c_int, [c_p, c_int, c_p, c_i64, c_p]),
     "hicgat_pairdist_bwd": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p, c_sz, c_p]),
-    "hicgat_pairdist_mse_fused": (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_p,
-                                          c_p, c_sz, c_p]),
-    "hicgat_pairdist_mse_fused_band": (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,
-                                               c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "hicgat_pairdist_mse_fused": (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,
+                                          c_p, c_p, c_p, c_p, c_sz, c_p]),
     "hicgat_pairdist_finalize": (c_int, [c_int, c_int, c_p, c_p, c_p]),
-    "hicgat_pairdist_finalize_rows": (c_int, [c_int, c_int, c_p, c_p, c_p, c_int, c_int, c_p, c_p]),
-    "hicgat_pairdist_finalize_rows_ex": (c_int, [c_int, c_int, c_p, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
+    "hicgat_pairdist_finalize_rows": (c_int, [c_int, c_int, c_p, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
     "hicgat_pairdist_num_tiles": (c_i64, [c_int, c_int]),
     "hicgat_pairdist_workspace_bytes": (c_sz, [c_int, c_int]),
-    "hicgat_pairdist_mse_fused_support": (c_int, [c_p, c_int, c_f, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_p,
-                                                  c_sz, c_p]),
+    "hicgat_pairdist_mse_fused_support": (c_int, [c_p, c_p, c_int, c_f, c_p, c_p, c_p, c_p, c_i64, c_i64,
+                                                  c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "hicgat_pairdist_support_workspace_bytes": (c_sz, [c_int]),
     "hicgat_xagg_vec_bytes": (c_sz, []),
-    "hicgat_xagg_logits": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
-    "hicgat_xagg_logits_zero": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_i64,
-                                        c_p, c_p]),
-    "hicgat_xagg_logits_zero_pack": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
-                                             c_i64, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "hicgat_xagg_logits": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
+                                   c_i64, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "hicgat_xagg_fwd": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_f, c_p, c_p,
                                 c_p]),
     "hicgat_xagg_bias_relu": (c_int, [c_p, c_p, c_p, c_int, c_int, c_p]),
@@ -109,19 +97,12 @@ SIGNATURES = {
     "hicgat_xagg_edge_acc_blocks": (c_int, [c_int]),
     "hicgat_xagg_slab_workspace_bytes": (c_sz, []),
     "hicgat_xagg_slab_sum": (c_int, [c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "hicgat_xagg_param_finish": (c_int, [c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
-    "hicgat_xagg_param_finish_seg": (c_int, [c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_int, c_int, c_int, c_p, c_p,
-                                             c_p, c_p]),
-    "hicgat_pairdist_mse_fused_support_range": (c_int, [c_p, c_int, c_f, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int,
-                                                        c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "hicgat_pairdist_mse_fused_support_range_ex": (c_int, [c_p, c_p, c_int, c_f, c_p, c_p, c_p, c_p, c_i64, c_i64,
-                                                           c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "hicgat_xagg_param_finish": (c_int, [c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_int, c_int, c_int, c_p, c_p,
+                                         c_p, c_p]),
     "hicgat_truth_support": (c_int, [c_p, c_int, c_i64, c_f, c_p, c_p, c_p, c_p, c_p]),
     "hicgat_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int,
-                            c_int, c_p, c_sz, c_p]),
+                            c_int, c_int, c_p, c_sz, c_p]),
     "hicgat_gemm_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
-    "hicgat_gemm_ex": (c_int, [c_int, c_int, c_int, c_int, c_int, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int,
-                               c_int, c_int, c_p, c_sz, c_p]),
     "hicgat_gemm_wgrad": (c_int, [c_int, c_int, c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p,
                                   c_sz, c_p]),
     "hicgat_gemm_wgrad_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
@@ -157,8 +138,7 @@ SIGNATURES = {
     "hicgat_n2v_sgns_epoch": (c_int, [c_p, c_int, c_int, c_p, c_p, c_int, c_int, c_int, c_int, c_f, c_f, c_int,
                                       c_int, c_u64, c_int, c_p, c_p, c_p]),
     "hicgat_adam_step": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_d, c_i64, c_p]),
-    "hicgat_adam_step_table": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_p, c_i64, c_p, c_p]),
-    "hicgat_adam_step_table_ex": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_p, c_i64, c_p, c_int, c_p]),
+    "hicgat_adam_step_table": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_p, c_i64, c_p, c_int, c_p]),
     "hicgat_step_begin": (c_int, [c_p, c_i64, c_p, c_p]),
     "hicgat_step_begin_pack": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "hicgat_act_dropout_fwd": (c_int, [c_p, c_i64, c_int, c_int, c_int, c_f, c_d, c_u64, c_p, c_i64, c_u32, c_i64,

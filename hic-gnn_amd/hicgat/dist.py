@@ -39,7 +39,7 @@ Three step forms (``mode``; "auto" picks xagg from P = 2, ``resolve_mode``):
 
 Loss (both forms): the truth in background + support form (``graph.SupportForm``, cont2dist's
 target: background 1 off the contact set), so the O(N^2) pass streams no truth: rank p takes the
-bulk over its tile range and the support rows of its block (``hicgat_pairdist_mse_fused_support_range``),
+bulk over its tile range and the support rows of its block (``hicgat_pairdist_mse_fused_support``),
 and the fp64 all-reduce sums the partial moments and dcoords.  A truth without a support form
 falls back to the dense band of the rank's tile range.
 

@@ -82,8 +82,8 @@ class HipKernels:
             # takes the small / unaligned cases)
             st = _lib.stream(x.device)
             with _timed("gat_linear_att"):
-                _lib.check(self.lib.hicgat_gemm_ex(0, 0, N, H * C, F, P(x), x.stride(0), P(W), W.stride(0), None, P(h),
-                                                   h.stride(0), 0, 1, self.gemm_impl, None, 0, st), "hicgat_gemm_ex")
+                _lib.check(self.lib.hicgat_gemm(0, 0, N, H * C, F, P(x), x.stride(0), P(W), W.stride(0), None, P(h),
+                                                h.stride(0), 0, 1, self.gemm_impl, None, 0, st), "hicgat_gemm")
                 _lib.check(self.lib.hicgat_gat_att_logits(P(h), P(att_l), P(att_r), N, H, C, P(a_src), P(a_dst), st),
                            "hicgat_gat_att_logits")
             return h, a_src, a_dst
@@ -103,13 +103,7 @@ class HipKernels:
 
     # -- a4 + a5 ----------------------------------------------------------------------------------
     def agg_fwd(self, rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, out, row_stats):
-        N = h.shape[0]
-        H = a_src.shape[1]
-        C = h.shape[1] // H
-        with _timed("gat_agg_fwd"):
-            _lib.check(self.lib.hicgat_gat_agg_fwd(P(rowptr), P(col), N, col.numel(), H, C, r0, r1, P(h), P(a_src),
-                                                   P(a_dst), P(bias), float(ns), P(out), P(row_stats),
-                                                   _lib.stream(h.device)), "hicgat_gat_agg_fwd")
+        self.agg_fwd_act(rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, 0, out, None, row_stats)
 
     def agg_fwd_act(self, rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, act, out, out2, row_stats):
         """Training form: ``act`` 1 = relu epilogue; ``out2`` (or None) = sum alpha lrelu' h."""
@@ -117,10 +111,9 @@ class HipKernels:
         H = a_src.shape[1]
         C = h.shape[1] // H
         with _timed("gat_agg_fwd"):
-            _lib.check(self.lib.hicgat_gat_agg_fwd_act(P(rowptr), P(col), N, col.numel(), H, C, r0, r1, P(h),
-                                                       P(a_src), P(a_dst), P(bias), float(ns), int(act), P(out),
-                                                       P(out2), P(row_stats), _lib.stream(h.device)),
-                       "hicgat_gat_agg_fwd_act")
+            _lib.check(self.lib.hicgat_gat_agg_fwd(P(rowptr), P(col), N, col.numel(), H, C, r0, r1, P(h), P(a_src),
+                                                   P(a_dst), P(bias), float(ns), int(act), P(out), P(out2),
+                                                   P(row_stats), _lib.stream(h.device)), "hicgat_gat_agg_fwd")
 
     def agg_fwd_tiled(self, rowptr, col, tiles, h, a_src, a_dst, bias, ns, act, out, out2, row_stats):
         """``agg_fwd_act`` over rows [tiles.r0, tiles.r1) with the dense tiles on the matrix cores."""
@@ -186,12 +179,12 @@ class HipKernels:
         # row_stats / dout may be row-strided views (the packed all-gather buffer of hicgat.dist)
         assert row_stats.stride(1) == 1 and dout.stride(1) == 1
         with _timed("gat_agg_bwd_src"):
-            _lib.check(self.lib.hicgat_gat_agg_bwd_src_ex(P(rowptr), P(col), N, H, C, r0, r1, P(h), P(a_src),
-                                                          P(a_dst), P(row_stats), row_stats.stride(0), P(dout),
-                                                          dout.stride(0), P(att_l), P(att_r), float(ns), P(dh),
-                                                          P(da_src), self.SRC_ROUND_ROBIN if round_robin else 0,
-                                                          _lib.stream(h.device)),
-                       "hicgat_gat_agg_bwd_src_ex")
+            _lib.check(self.lib.hicgat_gat_agg_bwd_src(P(rowptr), P(col), N, H, C, r0, r1, P(h), P(a_src),
+                                                       P(a_dst), P(row_stats), row_stats.stride(0), P(dout),
+                                                       dout.stride(0), P(att_l), P(att_r), float(ns), P(dh),
+                                                       P(da_src), self.SRC_ROUND_ROBIN if round_robin else 0,
+                                                       _lib.stream(h.device)),
+                       "hicgat_gat_agg_bwd_src")
 
     def param_grad(self, h, dout, da_src, row_stats, H, out=None, accumulate=False):
         """Column sums over the given rows -> (datt_src [D], datt_dst [D], dbias [D]); ``out`` =
@@ -269,10 +262,10 @@ class HipKernels:
             assert W.is_contiguous() and W1c.is_contiguous() and W2c.is_contiguous()
             nb = buf.numel() * buf.element_size()
         with _timed("xagg_logits"):
-            _lib.check(self.lib.hicgat_xagg_logits_zero_pack(
+            _lib.check(self.lib.hicgat_xagg_logits(
                 P(x), P(W), P(att_l), P(att_r), N, F, H, C, P(vec), P(a_src), P(a_dst), P(zero),
                 0 if zero is None else zero.numel(), P(step_ctr), P(W1c), P(W2c), P(buf), nb,
-                _lib.stream(x.device)), "hicgat_xagg_logits_zero_pack")
+                _lib.stream(x.device)), "hicgat_xagg_logits")
 
     def xagg_fwd(self, rowptr, col, r0, r1, x, a_src, a_dst, ns, X4, row_stats):
         """Own rows [r0, r1): X4 [2, 2, r1 - r0, 512] = (xa, xa2) per head; row stats (global rows)."""
@@ -332,16 +325,13 @@ class HipKernels:
     def xagg_param_finish(self, W, att_l, att_r, g_src, g_dst, dW, datt_l, datt_r):
         """``g_src`` / ``g_dst``: [2 * 512] or, segmented, [segs, 2 * 512] views (the segments are added)."""
         H, C = att_l.shape[-2], att_l.shape[-1]
+        segs, seg_stride = 1, 0
         if g_src.dim() == 2:
             assert g_dst.shape == g_src.shape and g_src.stride(0) == g_dst.stride(0) and g_src.stride(1) == 1
-            _lib.check(self.lib.hicgat_xagg_param_finish_seg(P(W), P(att_l), P(att_r), P(g_src), P(g_dst),
-                                                             g_src.shape[0], g_src.stride(0), W.shape[1], H, C, P(dW),
-                                                             P(datt_l), P(datt_r), _lib.stream(W.device)),
-                       "hicgat_xagg_param_finish_seg")
-            return
-        _lib.check(self.lib.hicgat_xagg_param_finish(P(W), P(att_l), P(att_r), P(g_src), P(g_dst), W.shape[1], H, C,
-                                                     P(dW), P(datt_l), P(datt_r), _lib.stream(W.device)),
-                   "hicgat_xagg_param_finish")
+            segs, seg_stride = g_src.shape[0], g_src.stride(0)
+        _lib.check(self.lib.hicgat_xagg_param_finish(P(W), P(att_l), P(att_r), P(g_src), P(g_dst), segs, seg_stride,
+                                                     W.shape[1], H, C, P(dW), P(datt_l), P(datt_r),
+                                                     _lib.stream(W.device)), "hicgat_xagg_param_finish")
 
     # -- f1: SAGEConv (layers.py:41-79) --------------------------------------------------------------
     def sage_weights(self, A, rowptr, col):
@@ -371,19 +361,14 @@ class HipKernels:
         """``tbuf`` is the truth or a band of it starting at (row0, col0) (hicgat.dist)."""
         ws = _lib.workspace(self.lib.hicgat_pairdist_workspace_bytes(n, self.PD_TRI), coords.device)
         with _timed("pairdist_mse_fused"):
-            _lib.check(self.lib.hicgat_pairdist_mse_fused_band(
+            _lib.check(self.lib.hicgat_pairdist_mse_fused(
                 P(coords), P(tbuf), n, tbuf.shape[1], int(row0), tbuf.shape[0], int(col0), int(t0), int(t1),
                 int(kind), P(stats), P(loss), P(dcoords), P(ws), ws.numel(), _lib.stream(coords.device)),
-                "hicgat_pairdist_mse_fused_band")
+                "hicgat_pairdist_mse_fused")
 
     def fused_loss_support(self, coords, sf, n, kind, stats, loss, dcoords):
         """The fused loss over a truth in background + support form (``graph.SupportForm``)."""
-        ws = _lib.workspace(self.lib.hicgat_pairdist_support_workspace_bytes(n), coords.device)
-        with _timed("pairdist_mse_fused"):
-            _lib.check(self.lib.hicgat_pairdist_mse_fused_support_range_ex(
-                P(coords), None, n, sf.background, P(sf.rowptr), P(sf.col_buf), P(sf.val_buf), P(sf.diag), 0, -1, 0,
-                n, int(kind), P(stats), P(loss), P(dcoords), None, P(ws), ws.numel(),
-                _lib.stream(coords.device)), "hicgat_pairdist_mse_fused_support_range_ex")
+        self.fused_loss_support_range(coords, sf, n, kind, 0, -1, 0, n, stats, loss, dcoords)
 
     def fused_loss_support_range(self, coords, sf, n, kind, t0, t1, s0, s1, stats, loss, dcoords, cmap=None):
         """A rank's share of the background-form loss: bulk tiles [t0, t1), support rows [s0, s1)
@@ -394,10 +379,10 @@ class HipKernels:
         d32, d64 = (None, dcoords) if dcoords.dtype == torch.float64 else (dcoords, None)
         assert cmap is None or (cmap.dtype == torch.int32 and cmap.numel() == n)
         with _timed("pairdist_mse_fused"):
-            _lib.check(self.lib.hicgat_pairdist_mse_fused_support_range_ex(
+            _lib.check(self.lib.hicgat_pairdist_mse_fused_support(
                 P(coords), P(cmap), n, sf.background, P(sf.rowptr), P(sf.col_buf), P(sf.val_buf), P(sf.diag), int(t0),
                 int(t1), int(s0), int(s1), int(kind), P(stats), P(loss), P(d32), P(d64), P(ws), ws.numel(),
-                _lib.stream(coords.device)), "hicgat_pairdist_mse_fused_support_range_ex")
+                _lib.stream(coords.device)), "hicgat_pairdist_mse_fused_support")
 
     def loss_finalize(self, n, kind, stats, loss, dc64=None, r0=0, r1=0, dcoords=None, reorder=None):
         """mse / r / alpha / total from the (all-reduced) moments; with ``dc64`` also dcoords[r0:r1] =
@@ -411,10 +396,10 @@ class HipKernels:
         cbuf, gidx, cglob = reorder if reorder is not None else (None, None, None)
         if reorder is not None:
             assert cbuf.is_contiguous() and cglob.shape == (n, 3) and gidx.dtype == torch.int32 and gidx.numel() == n
-        _lib.check(self.lib.hicgat_pairdist_finalize_rows_ex(n, int(kind), P(stats), P(loss), P(dc64), int(r0), int(r1),
-                                                             P(dcoords), P(cbuf), P(gidx), P(cglob),
-                                                             _lib.stream(stats.device)),
-                   "hicgat_pairdist_finalize_rows_ex")
+        _lib.check(self.lib.hicgat_pairdist_finalize_rows(n, int(kind), P(stats), P(loss), P(dc64), int(r0), int(r1),
+                                                          P(dcoords), P(cbuf), P(gidx), P(cglob),
+                                                          _lib.stream(stats.device)),
+                   "hicgat_pairdist_finalize_rows")
 
     def pairdist_fwd(self, coords):
         n = coords.shape[0]
@@ -444,10 +429,10 @@ class HipKernels:
         if splits > 1:
             ws = _lib.workspace(self.lib.hicgat_gemm_workspace_bytes(M, N, splits), dev)
         with _timed(name):
-            _lib.check(self.lib.hicgat_gemm_ex(int(a_kmajor), int(b_kmajor), M, N, K, P(A), A.stride(0), P(B),
-                                               B.stride(0), P(bias), P(C), C.stride(0), int(accumulate), int(splits),
-                                               int(impl), P(ws), 0 if ws is None else ws.numel(), _lib.stream(dev)),
-                       "hicgat_gemm_ex")
+            _lib.check(self.lib.hicgat_gemm(int(a_kmajor), int(b_kmajor), M, N, K, P(A), A.stride(0), P(B),
+                                            B.stride(0), P(bias), P(C), C.stride(0), int(accumulate), int(splits),
+                                            int(impl), P(ws), 0 if ws is None else ws.numel(), _lib.stream(dev)),
+                       "hicgat_gemm")
         return C
 
     def wgrad(self, dy, x, W_out, b_out=None, accumulate=False, splits=1):
@@ -760,10 +745,10 @@ class HipKernels:
     # -- a10 --------------------------------------------------------------------------------------
     def adam_table(self, flat, grad, m, v, n, b1, b2, eps, table, step_ctr, counted=False):
         with _timed("adam"):
-            _lib.check(self.lib.hicgat_adam_step_table_ex(P(flat), P(grad), P(m), P(v), int(n), float(b1), float(b2),
-                                                          float(eps), P(table), table.shape[0], P(step_ctr),
-                                                          int(bool(counted)), _lib.stream(flat.device)),
-                       "hicgat_adam_step_table_ex")
+            _lib.check(self.lib.hicgat_adam_step_table(P(flat), P(grad), P(m), P(v), int(n), float(b1), float(b2),
+                                                       float(eps), P(table), table.shape[0], P(step_ctr),
+                                                       int(bool(counted)), _lib.stream(flat.device)),
+                       "hicgat_adam_step_table")
 
     def step_begin(self, grad, step_ctr=None, pack=None):
         """zero_grad of the flat gradient buffer + (step_ctr) the device step count's advance, one launch;

@@ -86,23 +86,18 @@ int hicgat_gat_att_logits(const float *h, const float *att_src, const float *att
  * other shapes return HICGAT_EUNSUPPORTED.  H == 2, C == 256 (the flagship's GATConv(512, 256,
  * heads=2), models.py:619) has entry kernels and launch parameters of its own around the per-row bodies
  * that every shape shares (gat_agg.hpp); the rest are launched from gat_generic.hip.
- * The same set holds for hicgat_gat_agg_fwd_act, hicgat_gat_agg_bwd_dst, hicgat_gat_agg_bwd_rows and
- * hicgat_gat_agg_bwd_src / _ld / _ex; the tiled (hicgat_gat_agg_*_tiled) and aggregate-first
- * (hicgat_xagg_*) forms stay H == 2, C == 256. */
+ * The same set holds for hicgat_gat_agg_bwd_dst, hicgat_gat_agg_bwd_rows and hicgat_gat_agg_bwd_src;
+ * the tiled (hicgat_gat_agg_*_tiled) and aggregate-first (hicgat_xagg_*) forms stay H == 2, C == 256.
+ * nnz = rowptr[N] (checked >= 0 only).  bias [H*C].  act = 1 writes out = relu(sum + bias) (the relu
+ * that follows the GATConv at models.py:637), act = 0 the plain sum + bias (inference: act = 0,
+ * out2 = NULL).  out2 != NULL (training) also writes, from the same gathered rows, out2 [N, H*C] =
+ * sum_j alpha_ij lrelu'(e_ij) h_j and S3[i,h] = sum_j alpha_ij lrelu'(e_ij) into row_stats[i, 2H..3H)
+ * -- the inputs that let hicgat_gat_agg_bwd_rows form the destination half of the backward without a
+ * gather.  No other pointer may be NULL. */
 int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
                        int row_begin, int row_end, const float *h, const float *a_src,
-                       const float *a_dst, const float *bias, float neg_slope, float *out,
-                       float *row_stats, hicgat_stream_t stream);
-/* Training form of the same aggregation.  act = 1 writes out = relu(sum + bias) (the relu that
- * follows the GATConv at models.py:637), act = 0 the plain sum + bias.  out2 != NULL (training)
- * also writes, from the same gathered rows, out2 [N, H*C] = sum_j alpha_ij lrelu'(e_ij) h_j and
- * S3[i,h] = sum_j alpha_ij lrelu'(e_ij) into row_stats[i, 2H..3H) -- the inputs that let
- * hicgat_gat_agg_bwd_rows form the destination half of the backward without a gather.
- * Supported shapes: as hicgat_gat_agg_fwd. */
-int hicgat_gat_agg_fwd_act(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
-                           int row_begin, int row_end, const float *h, const float *a_src,
-                           const float *a_dst, const float *bias, float neg_slope, int act,
-                           float *out, float *out2, float *row_stats, hicgat_stream_t stream);
+                       const float *a_dst, const float *bias, float neg_slope, int act,
+                       float *out, float *out2, float *row_stats, hicgat_stream_t stream);
 
 /* ---- a10 (part): backward of a4+a5 ----------------------------------------------------------
  * Pass 1 (destination side, rows of the range):  g_ij = <dout[i,h,:], h[j,h,:]>,
@@ -118,7 +113,7 @@ int hicgat_gat_agg_bwd_dst(const int32_t *rowptr, const int32_t *col, int N, int
                            int row_begin, int row_end, const float *h, const float *a_src,
                            const float *a_dst, const float *dout, float neg_slope,
                            float *row_stats, hicgat_stream_t stream);
-/* Pass 1 without a gather, after hicgat_gat_agg_fwd_act(..., out2, ...) (same row_stats):
+/* Pass 1 without a gather, after hicgat_gat_agg_fwd with out2 (same row_stats):
  *   dout = g * [y > 0] (act = 1, written to dout with row stride ld_dout floats; torch's relu
  *   backward on the output y) or g
  *   (act = 0, dout unused); delta = <dout, y - bias>; da_dst = <dout, out2> - delta * S3,
@@ -126,29 +121,19 @@ int hicgat_gat_agg_bwd_dst(const int32_t *rowptr, const int32_t *col, int N, int
 int hicgat_gat_agg_bwd_rows(int N, int H, int C, int row_begin, int row_end, int act, const float *g,
                             const float *y, const float *bias, const float *out2, float *dout,
                             int64_t ld_dout, float *row_stats, hicgat_stream_t stream);
-int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H, int C,
-                           int row_begin, int row_end, const float *h, const float *a_src,
-                           const float *a_dst, const float *row_stats, const float *dout,
-                           const float *att_src, const float *att_dst, float neg_slope, float *dh,
-                           float *da_src, hicgat_stream_t stream);
-/* The same with strided rows: dout row i at dout + i*ld_dout, row_stats row i at
- * row_stats + i*ld_stats (floats, multiples of 4) -- e.g. one all-gathered [dout | row stats]
- * buffer per row (hicgat.dist). */
-int hicgat_gat_agg_bwd_src_ld(const int32_t *rowptr, const int32_t *col, int N, int H, int C,
-                              int row_begin, int row_end, const float *h, const float *a_src,
-                              const float *a_dst, const float *row_stats, int64_t ld_stats,
-                              const float *dout, int64_t ld_dout, const float *att_src,
-                              const float *att_dst, float neg_slope, float *dh, float *da_src,
-                              hicgat_stream_t stream);
-/* The same with launch flags: HICGAT_SRC_ROUND_ROBIN spreads consecutive row blocks over the XCDs
- * instead of giving each XCD a contiguous row range (the multi-GPU "slab" pass, hicgat.dist, whose
- * heavy rows are one contiguous block); flags 0 = hicgat_gat_agg_bwd_src_ld. */
+/* Pass 2 (above): dh [N, H*C] and da_src [N, H], rows of the range written.  Row i of dout is at
+ * dout + i*ld_dout and of row_stats at row_stats + i*ld_stats (floats; ld_dout >= H*C, ld_stats >= 4H,
+ * both multiples of 4): contiguous tensors pass H*C and 4H, hicgat.dist one all-gathered
+ * [dout | row stats] buffer per row.  att_src / att_dst [H, C].  No pointer may be NULL.  flags: 0, or
+ * HICGAT_SRC_ROUND_ROBIN, which spreads consecutive row blocks over the XCDs instead of giving each
+ * XCD a contiguous row range (the multi-GPU "slab" pass, hicgat.dist, whose heavy rows are one
+ * contiguous block); any other bit: HICGAT_EINVAL. */
 enum { HICGAT_SRC_ROUND_ROBIN = 1 };
-int hicgat_gat_agg_bwd_src_ex(const int32_t *rowptr, const int32_t *col, int N, int H, int C, int row_begin,
-                              int row_end, const float *h, const float *a_src, const float *a_dst,
-                              const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
-                              const float *att_src, const float *att_dst, float neg_slope, float *dh, float *da_src,
-                              int flags, hicgat_stream_t stream);
+int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H, int C, int row_begin,
+                           int row_end, const float *h, const float *a_src, const float *a_dst,
+                           const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
+                           const float *att_src, const float *att_dst, float neg_slope, float *dh, float *da_src,
+                           int flags, hicgat_stream_t stream);
 /* ---- the attention weights as an output, and their backward (gat_attn.hip) ---------------------
  * Reference: PyG 1.7.2 GATConv.forward(x, edge_index, return_attention_weights=True), which
  * models.py:1122 calls: alpha [nnz, H] in the order of the self-looped CSR, an autograd tensor there.
@@ -158,7 +143,7 @@ int hicgat_gat_agg_bwd_src_ex(const int32_t *rowptr, const int32_t *col, int N, 
  *     i's sorted columns); its own inverse, the identity on the self loops; -1 where (i, r) is
  *     missing (the CSR is not structurally symmetric).  Built once per graph.
  *   hicgat_gat_alpha: alpha[e, h] = exp(lrelu(a_src[j] + a_dst[i]) - max_i) / (sum_i + 1e-16) from
- *     row_stats[i, 0..2H) (after hicgat_gat_agg_fwd*); gathers no h rows.
+ *     row_stats[i, 0..2H) (after hicgat_gat_agg_fwd or its tiled form); gathers no h rows.
  * For G = dL/dalpha [nnz, H], with s = lrelu'(a_src[j] + a_dst[i]):
  *   hicgat_gat_alpha_bwd_dst, row i: c[i, h] = sum_j alpha_ij G_ij and
  *     da_dst_g[i, h] = sum_j alpha_ij s_ij (G_ij - c[i, h])            (both [N, H], written).
@@ -188,10 +173,17 @@ int hicgat_gat_alpha_bwd_src(const int32_t *rowptr, const int32_t *col, const in
  * numbering whose rowptr[row_begin] = 0 (hicgat.dist.ShardPlan.own_csr); per-row outputs marked
  * "local" are indexed i - row_begin, row_stats by the global row.
  *   hicgat_xagg_logits: vec [4][512] = W_h^T att_src^h (h = 0, 1), W_h^T att_dst^h; a_src / a_dst
- *     [N][2] = x . vec for all N rows (workspace vec: hicgat_xagg_vec_bytes()).
+ *     [N][2] = x . vec for all N rows (workspace vec: hicgat_xagg_vec_bytes()).  Its first launch
+ *     can carry the step's other first-launch work, each part selected by a pointer (NULL: left out):
+ *     zero_buf (16-B aligned; zero_n = 0 with NULL): zero_buf[0, zero_n) = 0, a step's flat gradient
+ *     buffer (the optimizer's zero_grad, HiC-GNN_main.py:124);  step_counter: the optimizer's device
+ *     step count += 1 (the step's Adam then calls hicgat_adam_step_table with counted = 1);  pack: the
+ *     head-fused tail's packed weights of W1c, W2c and Wh = W (hicgat_tail_pack's layout and
+ *     pack_bytes rule; W1c / W2c are read only with pack), so the sharded step's tail kernels need no
+ *     pack launch of their own.  Logits alone: NULL, 0, NULL, NULL, NULL, NULL, 0.
  *   hicgat_xagg_fwd: softmax statistics (row_stats [N][8]: max, sum at [0:4], S3 at [4:6]) and
  *     X4 [2 heads][2 kinds][rows][512] (local): kind 0 xa = sum alpha x_j, kind 1 xa2 = sum alpha
- *     lrelu'(e) x_j.  The caller then forms [out; out2] per head = [xa; xa2] W_h^T (hicgat_gemm_ex).
+ *     lrelu'(e) x_j.  The caller then forms [out; out2] per head = [xa; xa2] W_h^T (hicgat_gemm).
  *   hicgat_xagg_bias_relu: y0 += bias, o = relu(y0) over [rows][512].
  *   hicgat_xagg_rows_bwd: own rows (local row_stats view): dout = g [y0 > 0] (act 1) or g,
  *     delta^h = <dout^h, y0^h - bias^h> into row_stats[4:6]; the forward's S3 moves to [6:8].
@@ -204,24 +196,15 @@ int hicgat_gat_alpha_bwd_src(const int32_t *rowptr, const int32_t *col, const in
  *     g_src [2][512] = sum_j da_src_j^h x_j (x: all N rows), fixed-order partial sums
  *     (workspace hicgat_xagg_slab_workspace_bytes()).
  *   hicgat_xagg_param_finish: dW[256h + c][:] += att_src^h[c] g_src[h][:] + att_dst^h[c] g_dst[h][:],
- *     datt_src^h[c] += <W[256h + c][:], g_src[h][:]>, datt_dst likewise (g [2][512]: sum_j da_j^h x_j). */
+ *     datt_src^h[c] += <W[256h + c][:], g_src[h][:]>, datt_dst likewise, where g [2][512] = sum_j
+ *     da_j^h x_j is given in `segs` >= 1 segments (the segmented column sums of
+ *     hicgat_param_grads_grouped): g_src = sum over s of g_src + s * seg_stride (floats; >= 1024 when
+ *     segs > 1), g_dst likewise, added in segment order.  One flat g: segs = 1, seg_stride = 0. */
 size_t hicgat_xagg_vec_bytes(void);
 int hicgat_xagg_logits(const float *x, const float *W, const float *att_src, const float *att_dst, int N, int F,
-                       int H, int C, float *vec, float *a_src, float *a_dst, hicgat_stream_t stream);
-/* hicgat_xagg_logits that also zeroes zero_buf[0, zero_n) (a step's flat gradient buffer: the
- * optimizer's zero_grad, HiC-GNN_main.py:124) in its first launch -- one launch fewer per step --
- * and, with step_counter (NULL: none), advances the optimizer's device step count there (the step's
- * Adam then calls hicgat_adam_step_table_ex with counted = 1). */
-int hicgat_xagg_logits_zero(const float *x, const float *W, const float *att_src, const float *att_dst, int N,
-                            int F, int H, int C, float *vec, float *a_src, float *a_dst, float *zero_buf,
-                            int64_t zero_n, int64_t *step_counter, hicgat_stream_t stream);
-/* hicgat_xagg_logits_zero that, with pack (NULL: none), also writes the head-fused tail's packed
- * weights of W1c, W2c and Wh = W (hicgat_tail_pack's layout and pack_bytes rule) in the same launch:
- * the sharded step's tail kernels then read them without a pack launch of their own. */
-int hicgat_xagg_logits_zero_pack(const float *x, const float *W, const float *att_src, const float *att_dst, int N,
-                                 int F, int H, int C, float *vec, float *a_src, float *a_dst, float *zero_buf,
-                                 int64_t zero_n, int64_t *step_counter, const float *W1c, const float *W2c, void *pack,
-                                 size_t pack_bytes, hicgat_stream_t stream);
+                       int H, int C, float *vec, float *a_src, float *a_dst, float *zero_buf, int64_t zero_n,
+                       int64_t *step_counter, const float *W1c, const float *W2c, void *pack, size_t pack_bytes,
+                       hicgat_stream_t stream);
 int hicgat_xagg_fwd(const int32_t *rowptr, const int32_t *col, int N, int F, int H, int C, int row_begin,
                     int row_end, const float *x, const float *a_src, const float *a_dst, float neg_slope, float *X4,
                     float *row_stats, hicgat_stream_t stream);
@@ -246,16 +229,11 @@ int hicgat_xagg_slab_sum(const int32_t *rowptr_s, const int32_t *perm, int N, co
                          float *da_src, float *g_src, void *workspace, size_t workspace_bytes,
                          hicgat_stream_t stream);
 int hicgat_xagg_param_finish(const float *W, const float *att_src, const float *att_dst, const float *g_src,
-                             const float *g_dst, int F, int H, int C, float *dW, float *datt_src, float *datt_dst,
-                             hicgat_stream_t stream);
-/* The same with g in `segs` segments (the segmented column sums of hicgat_param_grads_grouped):
- * g_src = sum over s of g_src + s * seg_stride (floats), g_dst likewise, added in segment order. */
-int hicgat_xagg_param_finish_seg(const float *W, const float *att_src, const float *att_dst, const float *g_src,
-                                 const float *g_dst, int segs, int64_t seg_stride, int F, int H, int C, float *dW,
-                                 float *datt_src, float *datt_dst, hicgat_stream_t stream);
+                             const float *g_dst, int segs, int64_t seg_stride, int F, int H, int C, float *dW,
+                             float *datt_src, float *datt_dst, hicgat_stream_t stream);
 
 /* ---- a4+a5 and the source pass with the dense tiles on the matrix cores (gat_tiles.hip) -------
- * The same results as hicgat_gat_agg_fwd_act / hicgat_gat_agg_bwd_src_ld (fp32; the tiles' sums are
+ * The same results as hicgat_gat_agg_fwd / hicgat_gat_agg_bwd_src (fp32; the tiles' sums are
  * added in another order), with the edge set split in two:
  *   tiles: rows [row_begin, row_end) in blocks of 32 (block b = rows row_begin + 32b ..);
  *     tptr [nrb + 1] (nrb = ceil((row_end - row_begin) / 32)) indexes tcol [ntiles] (a 32-column
@@ -309,9 +287,13 @@ int hicgat_pairdist_bwd(const float *coords, const float *G, int N, int64_t ldg,
 
 /* ---- a7+a8+a9 fused: distance + MSE + Pearson moments + d(MSE)/dcoords, D never stored ------
  * Reference: out = cdist(coords) (models.py:661); MSELoss()(out, truth) (HiC-GNN_main.py:127);
- * pearsonr / alpha / total (HiC_GAT_generalize_directly.py:210-225).  T is the SYMMETRIC truth
- * (leading dim ldt); only upper-triangle tiles [tile_begin, tile_end) of the 128x128 tiling are
- * read (pass 0, -1 for all).  Outputs:
+ * pearsonr / alpha / total (HiC_GAT_generalize_directly.py:210-225).  T is the SYMMETRIC truth or a
+ * BAND of it (a rank's share, hicgat.dist): rows [t_row0, t_row0 + t_rows) and columns [t_col0,
+ * t_col0 + ldt) of the N x N truth, element (i, j) at T[(i - t_row0) * ldt + (j - t_col0)]; the whole
+ * truth is t_row0 = 0, t_rows = N, t_col0 = 0, ldt >= N.  Only upper-triangle tiles [tile_begin,
+ * tile_end) of the 128x128 tiling are read (pass 0, -1 for all); the band must cover every pair of
+ * the tile range: rows of its tile-rows I0..I1 and columns from I0*128 on, ldt >= N - t_col0 (else
+ * HICGAT_EINVAL).  dcoords may be NULL (no gradient).  Outputs:
  *   stats[12] (float64): 0 sum_{i<j}(d-t)^2, 1 sum d, 2 sum d^2, 3 sum dt, 4 sum t, 5 sum t^2,
  *     6 sum_i T_ii^2 (moments 0..6 over the tile range; a multi-GPU caller all-reduces them and
  *     calls hicgat_pairdist_finalize), 7 mse = (2*[0] + [6])/N^2, 8 pearson r over i<j,
@@ -326,71 +308,52 @@ int hicgat_pairdist_bwd(const float *coords, const float *G, int N, int64_t ldg,
  *     d(mse) (loss_kind 0, 1: the Pearson term carries no gradient in the reference) or
  *     float32(0.1 / M) * sum_j sign(d_ij - t_ij) (c_i - c_j) / d_ij, sign(0) = 0 (loss_kind 2).
  * workspace: hicgat_pairdist_workspace_bytes(N, HICGAT_PD_TRI). */
-int hicgat_pairdist_mse_fused(const float *coords, const float *T, int N, int64_t ldt,
-                              int64_t tile_begin, int64_t tile_end, int loss_kind, double *stats,
-                              float *loss, float *dcoords, void *workspace, size_t workspace_bytes,
-                              hicgat_stream_t stream);
-/* The same over a BAND of the truth (a rank's share, hicgat.dist): T holds rows
- * [t_row0, t_row0 + t_rows) and columns [t_col0, t_col0 + ldt) of the N x N truth, element (i, j) at
- * T[(i - t_row0) * ldt + (j - t_col0)].  The band must cover every pair of the tile range: rows of
- * its tile-rows I0..I1 and columns from I0*128 on (else HICGAT_EINVAL). */
-int hicgat_pairdist_mse_fused_band(const float *coords, const float *T, int N, int64_t ldt,
-                                   int64_t t_row0, int64_t t_rows, int64_t t_col0, int64_t tile_begin,
-                                   int64_t tile_end, int loss_kind, double *stats, float *loss,
-                                   float *dcoords, void *workspace, size_t workspace_bytes,
-                                   hicgat_stream_t stream);
+int hicgat_pairdist_mse_fused(const float *coords, const float *T, int N, int64_t ldt, int64_t t_row0,
+                              int64_t t_rows, int64_t t_col0, int64_t tile_begin, int64_t tile_end,
+                              int loss_kind, double *stats, float *loss, float *dcoords, void *workspace,
+                              size_t workspace_bytes, hicgat_stream_t stream);
+/* stats[7..11] and loss from the (all-reduced) moments stats[0..6], as above. */
 int hicgat_pairdist_finalize(int N, int loss_kind, double *stats, float *loss, hicgat_stream_t stream);
 /* hicgat_pairdist_finalize + dcoords[r][c] = (float)dc64[r][c] for rows [row_begin, row_end) of the
- * (all-reduced) fp64 coordinate gradient [N][3], in one launch (a rank's rows for its tail backward). */
-int hicgat_pairdist_finalize_rows(int N, int loss_kind, double *stats, float *loss, const double *dc64, int row_begin,
-                                  int row_end, float *dcoords, hicgat_stream_t stream);
-/* The same; with cbuf (the padded all-gather coordinates [P*R][3]) also cglob[i] = cbuf[gidx[i]]
- * (i < N: the coordinates in global row order, hicgat.dist's step() output) in the same launch. */
-int hicgat_pairdist_finalize_rows_ex(int N, int loss_kind, double *stats, float *loss, const double *dc64,
-                                     int row_begin, int row_end, float *dcoords, const float *cbuf,
-                                     const int32_t *gidx, float *cglob, hicgat_stream_t stream);
+ * (all-reduced) fp64 coordinate gradient [N][3], in one launch (a rank's rows for its tail backward;
+ * dc64 / dcoords may be NULL for an empty range).  With cbuf (NULL: none, then gidx and cglob are
+ * unused; the padded all-gather coordinates [P*R][3]) also cglob[i] = cbuf[gidx[i]] (i < N: the
+ * coordinates in global row order, hicgat.dist's step() output) in the same launch. */
+int hicgat_pairdist_finalize_rows(int N, int loss_kind, double *stats, float *loss, const double *dc64,
+                                  int row_begin, int row_end, float *dcoords, const float *cbuf,
+                                  const int32_t *gidx, float *cglob, hicgat_stream_t stream);
 /* Tile count and workspace of the two tilings, mode HICGAT_PD_TRI (the fused loss: upper-triangle
  * 128x128 tiles, nb(nb+1)/2) or HICGAT_PD_SQUARE (hicgat_pairdist_bwd: nb*nb), nb = ceil(N/128). */
 enum { HICGAT_PD_SQUARE = 0, HICGAT_PD_TRI = 1 };
 int64_t hicgat_pairdist_num_tiles(int N, int mode);
 size_t hicgat_pairdist_workspace_bytes(int N, int mode);
-/* The same fused loss (all tiles, stats / loss / dcoords as above) for a truth given in BACKGROUND
- * form: T[i][j] = background for i != j except at the support -- a symmetric CSR (rowptr [N+1],
- * sorted col, val = T there, no diagonal entries) -- and T[i][i] = diag[i].  cont2dist's target
- * (utils.py:75-80) is of this form with background 1 (zero contacts: inf -> max -> 1) and the
- * support = the contacts, so the O(N^2) pass reads no truth at all: it takes every pair at the
- * background value and a pass over the support adds the difference (same sums up to fp32 /
- * fp64 reassociation).  Build the form with hicgat_truth_support.
+/* The same fused loss (same reference call sites; stats / loss / dcoords as above) for a truth given
+ * in BACKGROUND form: T[i][j] = background for i != j except at the support -- a symmetric CSR
+ * (rowptr [N+1], sorted col, val = T there, no diagonal entries) -- and T[i][i] = diag[i].
+ * cont2dist's target (utils.py:75-80) is of this form with background 1 (zero contacts: inf -> max
+ * -> 1) and the support = the contacts, so the O(N^2) pass reads no truth at all: it takes every
+ * pair at the background value and a pass over the support adds the difference (same sums up to
+ * fp32 / fp64 reassociation).  Build the form with hicgat_truth_support.
+ * The call covers a SHARE of the pairs: the bulk over the upper-triangle tiles [tile_begin,
+ * tile_end) and the support rows [support_row_begin, support_row_end) (their entries j != i and
+ * their diagonal); 0, -1, 0, N is the whole loss on one GPU.  For a rank of hicgat.dist, stats[0..6]
+ * and dcoords [N,3] are its share's partial sums (the sum over shares that cover every tile and
+ * every row once is the whole loss: the caller all-reduces stats[0..6] + dcoords and calls
+ * hicgat_pairdist_finalize).
+ * cmap (NULL: row g of coords is global row g): cmap [N] maps global row g to its row in coords (the
+ * sharded step's padded [P*R, 3] all-gather buffer, so no reorder launch before the loss).
+ * dcoords / dcoords64: either may be NULL.  dcoords64 (instead of dcoords): the same fp32 gradient
+ * values widened to fp64, e.g. right behind stats[12] in one fp64 buffer that the caller all-reduces
+ * as a whole; with dcoords64 and at most 4096 tiles + support blocks in the share, stats[7..11] and
+ * loss are not written (the caller's finalize after the all-reduce sets them).
  * workspace: hicgat_pairdist_support_workspace_bytes(N). */
-int hicgat_pairdist_mse_fused_support(const float *coords, int N, float background, const int32_t *rowptr,
-                                      const int32_t *col, const float *val, const float *diag, int loss_kind,
-                                      double *stats, float *loss, float *dcoords, void *workspace,
-                                      size_t workspace_bytes, hicgat_stream_t stream);
+int hicgat_pairdist_mse_fused_support(const float *coords, const int32_t *cmap, int N, float background,
+                                      const int32_t *rowptr, const int32_t *col, const float *val,
+                                      const float *diag, int64_t tile_begin, int64_t tile_end,
+                                      int support_row_begin, int support_row_end, int loss_kind,
+                                      double *stats, float *loss, float *dcoords, double *dcoords64,
+                                      void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
 size_t hicgat_pairdist_support_workspace_bytes(int N);
-/* The background-form loss over a SHARE of the pairs (a rank of hicgat.dist): the bulk over the
- * upper-triangle tiles [tile_begin, tile_end) and the support rows [support_row_begin,
- * support_row_end) (their entries j != i and their diagonal).  stats[0..6] and dcoords [N,3] are
- * that share's partial sums (the sum over shares that cover every tile and every row once is the
- * whole loss: a caller all-reduces stats[0..6] + dcoords and calls hicgat_pairdist_finalize);
- * 0, -1, 0, N is hicgat_pairdist_mse_fused_support.  dcoords64 (instead of dcoords): the same
- * fp32 gradient values widened to fp64, e.g. right behind stats[12] in one fp64 buffer that the
- * caller all-reduces as a whole; with dcoords64 and at most 4096 tiles + support blocks in the share,
- * stats[7..11] and loss are not written (the caller's finalize after the all-reduce sets them).
- * Same workspace. */
-int hicgat_pairdist_mse_fused_support_range(const float *coords, int N, float background, const int32_t *rowptr,
-                                            const int32_t *col, const float *val, const float *diag,
-                                            int64_t tile_begin, int64_t tile_end, int support_row_begin,
-                                            int support_row_end, int loss_kind, double *stats, float *loss,
-                                            float *dcoords, double *dcoords64, void *workspace,
-                                            size_t workspace_bytes, hicgat_stream_t stream);
-/* The same with cmap (NULL = as above): cmap [N] maps global row g to its row in ``coords`` (the
- * sharded step's padded [P*R, 3] all-gather buffer, so no reorder launch before the loss). */
-int hicgat_pairdist_mse_fused_support_range_ex(const float *coords, const int32_t *cmap, int N, float background,
-                                               const int32_t *rowptr, const int32_t *col, const float *val,
-                                               const float *diag, int64_t tile_begin, int64_t tile_end,
-                                               int support_row_begin, int support_row_end, int loss_kind,
-                                               double *stats, float *loss, float *dcoords, double *dcoords64,
-                                               void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
 /* The background form of a symmetric N x N fp32 truth T (leading dim ldt): the sorted CSR of the
  * off-diagonal entries != background, their values, and the diagonal.  Two calls, as
  * hicgat_csr_from_dense: col == NULL fills rowptr (the counts, scanned); then col / val / diag. */
@@ -402,19 +365,16 @@ int hicgat_truth_support(const float *T, int N, int64_t ldt, float background, i
  *   A^T of A [K,M];  op(B) = B^T of B [N,K] or, with b_kmajor, B [K,N].
  *   Linear forward Y = X W^T + b (0,0); input grad dX = dY W (0,1); weight grad dW = dY^T X (1,1).
  * accumulate != 0 adds into C (a parameter's .grad).  splits > 1 splits K over workgroups into fp32
- * slabs (workspace: hicgat_gemm_workspace_bytes) added in split order: deterministic. */
+ * slabs (workspace: hicgat_gemm_workspace_bytes; NULL, 0 with splits = 1) added in split order:
+ * deterministic.  bias may be NULL.  impl names the matrix-core arithmetic: HICGAT_GEMM_AUTO (the
+ * default) = HICGAT_GEMM_F32, the only one: v_mfma_f32_32x32x2_f32, fp32 products, fp32 accumulate.
+ * HICGAT_GEMM_X3 (a three-way bf16 operand split on the bf16 matrix cores, round 1-3) measured slower
+ * per step and was removed: HICGAT_EUNSUPPORTED. */
+enum { HICGAT_GEMM_AUTO = 0, HICGAT_GEMM_F32 = 1, HICGAT_GEMM_X3 = 2 };
 int hicgat_gemm(int a_kmajor, int b_kmajor, int M, int N, int K, const float *A, int64_t lda,
                 const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
-                int splits, void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
+                int splits, int impl, void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
 size_t hicgat_gemm_workspace_bytes(int M, int N, int splits);
-/* The same GEMM with the matrix-core arithmetic named explicitly: HICGAT_GEMM_F32 (= AUTO, the
- * only one): v_mfma_f32_32x32x2_f32, fp32 products, fp32 accumulate.  HICGAT_GEMM_X3 (a three-way
- * bf16 operand split on the bf16 matrix cores, round 1-3) measured slower per step and was removed:
- * HICGAT_EUNSUPPORTED. */
-enum { HICGAT_GEMM_AUTO = 0, HICGAT_GEMM_F32 = 1, HICGAT_GEMM_X3 = 2 };
-int hicgat_gemm_ex(int a_kmajor, int b_kmajor, int M, int N, int K, const float *A, int64_t lda,
-                   const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
-                   int splits, int impl, void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
 /* Weight AND bias gradient of a Linear in one GEMM (replaces the dW GEMM + bias column sum of the
  * Linear backward, torch.nn.Linear via ATen addmm_backward / sum(0), models.py:637-659):
  *   dW[M,N] (+)= dY^T X  (dY [K,M] and X [K,N] row-major, K = node rows),
@@ -586,7 +546,7 @@ int hicgat_tail_bwd_fused_heads(const float *dcoords, int M, const float *Y1, co
  * (hicgat_gat_agg_bwd_rows on the dx rows while they are in LDS, same arithmetic, bitwise): no dx is
  * written; dout [M][512] = dx [y > 0] (act != 0) or dx, and row_stats[8i + 4 .. 8i + 8) = (delta,
  * da_dst) from the forward's S3 there, for y = the GATConv's relu output (the tail's input rows),
- * out2 and bias of hicgat_gat_agg_fwd_act.  One row per wave: HICGAT_EUNSUPPORTED unless the kernels
+ * out2 and bias of hicgat_gat_agg_fwd.  One row per wave: HICGAT_EUNSUPPORTED unless the kernels
  * run 16 waves (hicgat_tail_bwd_waves). */
 int hicgat_tail_bwd_fused_rows(const float *dcoords, int M, const float *Y1, const float *st1, const float *Y2,
                                const float *st2, const float *y3, const float *st3, const float *W4, const float *W3,
@@ -649,16 +609,15 @@ int hicgat_adam_step(float *param, const float *grad, float *exp_avg, float *exp
                      hicgat_stream_t stream);
 /* Graph-replayable form: the step count lives on the device (*step_counter = steps done so far,
  * incremented by the call), the per-step constants come from table[step] = (-lr/(1-b1^t),
- * sqrt(1-b2^t)) for t = step+1, computed on the host exactly like hicgat_adam_step does. */
+ * sqrt(1-b2^t)) for t = step+1, computed on the host exactly like hicgat_adam_step does.
+ * counted = 0: the call reads row *step_counter and increments the count in a launch of its own.
+ * counted = 1: this step's increment already happened in an earlier launch of the step
+ * (hicgat_step_begin, hicgat_step_begin_pack or hicgat_xagg_logits with step_counter), so the table
+ * row is *step_counter - 1 and no increment follows (one launch fewer).  No pointer may be NULL;
+ * param / grad / exp_avg / exp_avg_sq 16-B, table 8-B aligned. */
 int hicgat_adam_step_table(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
                            int64_t n, double beta1, double beta2, double eps, const float *table,
-                           int64_t table_len, int64_t *step_counter, hicgat_stream_t stream);
-/* The same; counted = 1: this step's increment of *step_counter already happened in an earlier
- * launch of the step (hicgat_xagg_logits_zero), so the table row is *step_counter - 1 and no
- * increment follows (one launch fewer); counted = 0 is hicgat_adam_step_table. */
-int hicgat_adam_step_table_ex(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
-                              int64_t n, double beta1, double beta2, double eps, const float *table,
-                              int64_t table_len, int64_t *step_counter, int counted, hicgat_stream_t stream);
+                           int64_t table_len, int64_t *step_counter, int counted, hicgat_stream_t stream);
 /* A step's first launch: grad[0, n) = 0 (zero_grad, HiC-GNN_main.py:124) and, with step_counter
  * (NULL: none), *step_counter += 1 (the step's Adam then uses counted = 1).  grad 16-B aligned. */
 int hicgat_step_begin(float *grad, int64_t n, int64_t *step_counter, hicgat_stream_t stream);

@@ -171,7 +171,7 @@ class CpuKernels:
                 o.copy_(r)
         return out
 
-    # -- GEMM / column sums (hicgat_gemm_ex, hicgat_colsum): the "xagg" step runs its GEMMs here ----
+    # -- GEMM / column sums (hicgat_gemm, hicgat_colsum): the "xagg" step runs its GEMMs here ----
     def gemm(self, a_kmajor, b_kmajor, M, N, K, A, B, C, bias=None, accumulate=False, splits=1, name="gemm",
              impl=None):
         opA = (A.t() if a_kmajor else A)[:M, :K].double()
@@ -351,7 +351,7 @@ class CpuKernels:
         self.loss_finalize(n, kind, stats, loss)
 
     def fused_loss_support_range(self, coords, sf, n, kind, t0, t1, s0, s1, stats, loss, dcoords):
-        """hicgat_pairdist_mse_fused_support_range: the bulk (every pair of the tile range at the
+        """hicgat_pairdist_mse_fused_support: the bulk (every pair of the tile range at the
         background value) + the support rows [s0, s1) (their differing entries and diagonal)."""
         nb = (n + BT - 1) // BT
         c = coords.double()

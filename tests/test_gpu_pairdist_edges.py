@@ -185,7 +185,7 @@ def _lds_image_form(G, n):
 
 
 def _sym_lds_image_form(tbuf, n, col0):
-    """hicgat_pairdist_mse_fused_band's condition for the LDS-image form."""
+    """hicgat_pairdist_mse_fused's condition for the LDS-image form."""
     nb = (n + R.BT - 1) // R.BT
     return (tbuf.is_contiguous() and tbuf.shape[1] % 4 == 0 and col0 % 4 == 0 and tbuf.data_ptr() % 16 == 0
             and tbuf.shape[1] >= nb * R.BT - col0)
@@ -289,7 +289,7 @@ def test_fused_loss_band_rejects_column_origin_past_first_tile_row():
     stats = torch.full((12,), EINVAL_SENTINEL, dtype=torch.float64, device=DEV)
     loss = torch.full((), EINVAL_SENTINEL, dtype=torch.float32, device=DEV)
     dc = torch.full_like(c, EINVAL_SENTINEL)
-    with pytest.raises(_lib.HicgatError, match="hicgat_pairdist_mse_fused_band failed: invalid argument"):
+    with pytest.raises(_lib.HicgatError, match="hicgat_pairdist_mse_fused failed: invalid argument"):
         hicgat.kernels.default().fused_loss(c, tbuf, n, KINDS["mse"], BAND["t0"], BAND["t1"], stats, loss, dc,
                                             row0=BAND["row0"], col0=129)
     torch.cuda.synchronize()

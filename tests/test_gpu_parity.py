@@ -885,8 +885,8 @@ def test_full_size_synth20000_properties():
     o = torch.empty(n, 512, device=DEV)
     rs = torch.empty(n, 8, device=DEV)
     _lib.check(lib.hicgat_gat_agg_fwd(_lib.ptr(adj.rowptr32), _lib.ptr(adj.col32), n, nnz, 2, 256, 0, n,
-                                      _lib.ptr(hconst), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(bias), 0.2,
-                                      _lib.ptr(o), _lib.ptr(rs), _lib.stream()), "agg")
+                                      _lib.ptr(hconst), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(bias), 0.2, 0,
+                                      _lib.ptr(o), None, _lib.ptr(rs), _lib.stream()), "agg")
     assert torch.allclose(o, 0.75 + bias.expand_as(o), rtol=0, atol=2e-6)
     tr = hicgat.Truth.from_contacts(A, 0.5)
     cc = torch.randn(n, 3, device=DEV).requires_grad_(True)

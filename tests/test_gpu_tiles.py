@@ -1,7 +1,7 @@
 """The dense-tile aggregation (csrc/gat_tiles.hip) against the gather kernels on the same inputs.
 
 The tiled path computes the same GATConv training-form forward (a4+a5: out, out2, row stats) and
-source-side backward (dh, da_src) as ``hicgat_gat_agg_fwd_act`` / ``hicgat_gat_agg_bwd_src_ld``,
+source-side backward (dh, da_src) as ``hicgat_gat_agg_fwd`` / ``hicgat_gat_agg_bwd_src``,
 with the edges of dense 32x32 tiles summed on the matrix cores in another order.  Graphs: ragged
 sizes (a partial last row block and column block), a banded Hi-C-like graph, a fully dense one,
 isolated rows (only the self loop), and tile thresholds from "every non-empty tile" (1) to "no tile"

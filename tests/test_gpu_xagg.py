@@ -262,7 +262,7 @@ def test_xagg_side_branch_equals_serial_order_with_a_real_reduce(n, world):
 @pytest.mark.parametrize("n,world", [(3000, 2), (20000, 8)])
 def test_xagg_step_pack_in_first_launch_is_bitwise(monkeypatch, n, world):
     """The head-fused tail's packed weights (W1c, W2c and lin_l's W) written by the xagg step's first
-    launch (hicgat_xagg_logits_zero_pack) against the tail forward's own hicgat_tail_pack launch
+    launch (hicgat_xagg_logits with pack) against the tail forward's own hicgat_tail_pack launch
     (ops.STEP_PACK = False): the captured step replays to the same loss, gradients and parameters bit
     for bit, and after each replay the buffer holds exactly the pack of that step's weights."""
     for p in (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),):

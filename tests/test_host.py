@@ -52,6 +52,84 @@ def test_ctypes_signatures_match_header_arity():
         assert len(args) == arity[name], (name, len(args), arity[name])
 
 
+def _header_prototypes():
+    """{symbol: (return type, [parameter types])} of every prototype in include/hicgat.h, as C type
+    strings without ``const`` and the parameter names ("float *", "int64_t", ...)."""
+    with open(os.path.join(ROOT, "include", "hicgat.h")) as fh:
+        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+
+    def ctype(decl, named):
+        decl = re.sub(r"\bconst\b", " ", decl)
+        if named:
+            decl = re.sub(r"\w+\s*$", "", decl)      # the parameter's name
+        return " ".join(decl.replace("*", " * ").split())
+
+    out = {}
+    for m in re.finditer(r"([\w\s\*]+?)\b(hicgat_\w+)\s*\(([^;{]*?)\)\s*;", text, re.S):
+        args = m.group(3).strip()
+        params = [] if args in ("", "void") else [ctype(a, True) for a in args.split(",")]
+        out[m.group(2)] = (ctype(m.group(1), False), params)
+    return out
+
+
+def test_ctypes_signatures_match_header_types():
+    """Every ctypes signature has the header's types, position by position, and its return type (a
+    c_float for a double, or a c_int for an int64_t, has the right count and fails only on a GPU,
+    if at all)."""
+    import ctypes
+    from hicgat import _lib
+    scalars = {"int": _lib.c_int, "int64_t": _lib.c_i64, "float": _lib.c_f, "double": _lib.c_d,
+               "size_t": _lib.c_sz, "uint64_t": _lib.c_u64, "uint32_t": _lib.c_u32, "hicgat_stream_t": _lib.c_p}
+    typed_pointers = {"hicgat_stream_t *": ctypes.POINTER(_lib.c_p), "hicgat_wgrad_job *": _lib.c_wjobs,
+                      "hicgat_colsum_job *": _lib.c_cjobs, "hicgat_gemm_job *": _lib.c_gjobs}
+    data = {"void", "float", "double", "int32_t", "uint32_t", "int64_t", "uint8_t", "unsigned long long"}
+
+    def expected(t, ret=False):
+        if ret and t == "char *":
+            return ctypes.c_char_p
+        if t in scalars:
+            return scalars[t]
+        if t in typed_pointers:
+            return typed_pointers[t]
+        assert t.endswith(" *") and t[:-2] in data, f"type {t!r} of the header has no ctypes mapping"
+        return _lib.c_p
+
+    protos = _header_prototypes()
+    assert set(protos) == set(_lib.SIGNATURES)
+    for name, (res, args) in _lib.SIGNATURES.items():
+        ret, params = protos[name]
+        assert res is expected(ret, ret=True), (name, "return", ret, res)
+        assert len(args) == len(params), name
+        for k, (a, t) in enumerate(zip(args, params)):
+            assert a is expected(t), (name, k, t, a)
+
+
+def _nm():
+    import shutil
+    llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-nm")
+    for tool in ("nm", "llvm-nm", llvm):
+        path = shutil.which(tool)
+        if path:
+            return path
+    return None
+
+
+def test_library_defines_exactly_the_header_symbols():
+    """The hicgat_* symbols libhicgat.so defines are the header's prototypes, in both directions (a
+    deleted prototype whose definition stayed behind is an export nobody declared)."""
+    import subprocess
+    from hicgat import _lib
+    nm = _nm()
+    if nm is None:
+        pytest.skip("no nm / llvm-nm on this machine")
+    _lib.load()
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("hicgat_")}
+    assert defined == set(_header_symbols()), (sorted(defined - set(_header_symbols())),
+                                               sorted(set(_header_symbols()) - defined))
+
+
 def test_row_split_policy():
     """kernels.row_splits: the single-GPU N = 20000 GEMM shapes are never K-split; a rank's shard
     (N = 20000 over P = 2..8) is split only as far as ~512 workgroups and never below 128-deep
