@@ -14,6 +14,12 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
       (BatchNorm1d + feature dropout)         ~ models.py:270-319 / :834-883
   hicgat.gat_models.GATNetHeadsChanged3LayersEmbeddingDim256Entropy (attention weights + entropy term)
                                               ~ models.py:1112-1148
+  hicgat.gat_models.LN_MODELS (six LayerNorm tails: ...ReLU_LayerNorm, ...LeakyReLU_LayerNorm, ...Embed512,
+      ...Embed512WithResiduals, GATNetSelectiveResiduals, GATNetSelectiveResidualsUpdatedLayerNorm)
+                                              ~ models.py:321-377 / :776-832 / :379-435 / :437-526 / :528-612 / :693-773
+  hicgat.ops.ln_act_res / dual_ln_act_res     ~ torch.nn.LayerNorm -> relu / leaky_relu / gelu (+ residual)
+                                                (-> torch.nn.LayerNorm)
+  hicgat.ops.act                              ~ F.gelu / F.leaky_relu
   hicgat.ops.bn_act_dropout                   ~ torch.nn.BatchNorm1d -> F.leaky_relu -> torch.nn.Dropout(p)
   hicgat.ops.act_dropout, hicgat.DropoutState ~ x.relu() / F.leaky_relu(x) -> torch.nn.Dropout(p)
   hicgat.graph.load_input / cont2dist / convert_to_matrix / Adj
@@ -36,6 +42,11 @@ from .gat_models import (GATNet, GATNetHeadsChanged3LayersEmbeddingDim256Entropy
                          GATNetHeadsChanged4LayersLeakyReLUHeads4,
                          GATNetHeadsChangedLeakyReLU, GATNetMoreReduced, GATNetReduced,
                          GATNetSelectiveResidualsUpdated, MODELS, Net)
+from .gat_models import (ALL_MODELS, LN_MODELS, GATNetHeadsChanged4LayersLeakyReLU_LayerNorm,  # noqa: F401
+                         GATNetHeadsChanged4LayersReLU_LayerNorm,
+                         GATNetHeadsChanged4LayersReLU_LayerNormEmbed512,
+                         GATNetHeadsChanged4LayersReLU_LayerNormEmbed512WithResiduals,
+                         GATNetSelectiveResiduals, GATNetSelectiveResidualsUpdatedLayerNorm)
 from .graph import Adj, Data, Truth, cont2dist, convert_to_matrix, load_input  # noqa: F401
 from .nn import GATConv, SAGEConv  # noqa: F401
 from .optim import FlatAdam  # noqa: F401

@@ -117,6 +117,14 @@ SIGNATURES = {
                                        c_p, c_int, c_p, c_sz, c_p]),
     "hicgat_ln_relu_res_workspace_bytes": (c_sz, [c_int]),
     "hicgat_ln_relu_res_bwd_params": (c_int, [c_int, c_p, c_p, c_int, c_p, c_sz, c_p]),
+    "hicgat_ln_act_res_fwd": (c_int, [c_p, c_i64, c_int, c_int, c_p, c_p, c_f, c_int, c_f, c_p, c_i64, c_p, c_p, c_f,
+                                      c_p, c_i64, c_p, c_p, c_p]),
+    "hicgat_ln_act_res_bwd": (c_int, [c_p, c_i64, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_int, c_f, c_p, c_i64,
+                                      c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_int, c_p, c_sz, c_p]),
+    "hicgat_ln_act_res_bwd_params": (c_int, [c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_sz, c_p]),
+    "hicgat_ln_act_res_workspace_bytes": (c_sz, [c_int, c_int]),
+    "hicgat_act_fwd": (c_int, [c_p, c_int, c_int, c_int, c_f, c_p, c_p]),
+    "hicgat_act_bwd": (c_int, [c_p, c_p, c_int, c_int, c_int, c_f, c_p, c_p]),
     "hicgat_tail_pack_bytes": (c_sz, []),
     "hicgat_tail_pack": (c_int, [c_p, c_p, c_p, c_p, c_sz, c_p]),
     "hicgat_tail_fwd_fused": (c_int, [c_p, c_i64, c_int] + [c_p] * 14 + [c_f] + [c_p] * 10 + [c_p, c_p]),

@@ -79,10 +79,8 @@ def generalize(model, list_trained, list_untrained, emb_trained, emb_untrained, 
     return metrics.dscc(coords, truth), coords
 
 
-def main(argv=None):
-    from . import kr, train
-    from .gat_models import MODELS
-    from .io import write_pdb
+def make_parser():
+    from .gat_models import ALL_MODELS
     p = argparse.ArgumentParser(description="Generalise a trained GAT-HiC model to another resolution "
                                             "(HiC_GAT_generalize_directly.py flags).")
     p.add_argument("list_trained")
@@ -94,13 +92,20 @@ def main(argv=None):
     p.add_argument("-lr", "--learningrate", type=float, default=0.001)
     p.add_argument("-thresh", "--loss_diff_threshold", type=float, default=1e-8)
     p.add_argument("--conversion", type=float, default=1.0)
-    p.add_argument("--model", default="GATNetSelectiveResidualsUpdated", choices=sorted(MODELS))
+    p.add_argument("--model", default="GATNetSelectiveResidualsUpdated", choices=sorted(ALL_MODELS))
     p.add_argument("--weights", default=None, help="trained state_dict (.pt); trained here when missing")
     p.add_argument("--steps", type=int, default=None)
     p.add_argument("--out", default=None, help="prefix for the weights / PDB / log files")
     p.add_argument("-print_interval", "--print_interval", type=int, default=10,
                    help="print MSE and dSCC every this many steps (:87)")
-    a = p.parse_args(argv)
+    return p
+
+
+def main(argv=None):
+    from . import kr, train
+    from .gat_models import model_class
+    from .io import write_pdb
+    a = make_parser().parse_args(argv)
     l1, l2 = np.loadtxt(a.list_trained), np.loadtxt(a.list_untrained)
     normed, emb = [], []
     for lst, src in ((l1, a.embeddings_trained), (l2, a.embeddings_untrained)):
@@ -113,7 +118,7 @@ def main(argv=None):
             emb.append(np.loadtxt(src))
         normed.append(kr.KRnorm(m)[0].cpu().numpy())
     e1, e2 = emb
-    model = MODELS[a.model]().cuda()
+    model = model_class(a.model)().cuda()
     if a.weights and os.path.isfile(a.weights):
         model.load_state_dict(torch.load(a.weights, weights_only=True))
     else:

@@ -381,6 +381,12 @@ class ShardedTrainer:
             # statistics over sharded rows would need a collective of their own
             raise NotImplementedError(f"ShardedTrainer does not run batch normalisation; {type(model).__name__} "
                                       f"normalises over all node rows (single-GPU hicgat.train only)")
+        from .gat_models import LN_MODELS
+        if type(model).__name__ in LN_MODELS:
+            # by name, before any collective: three of them have the flagship's norm_a / norm1 / norm2 and
+            # ops.fused_tail_ok would take them for it
+            raise NotImplementedError(f"ShardedTrainer does not run the LayerNorm tails of gat_models.LN_MODELS; "
+                                      f"{type(model).__name__} is single-GPU hicgat.train only")
         conv = getattr(model, "conv", None)
         shape =tuple(getattr(conv, a, None) for a in ("in_channels", "out_channels", "heads"))
         if shape != (512, 256, 2):

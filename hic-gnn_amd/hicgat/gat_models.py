@@ -29,6 +29,20 @@ One that returns its attention weights and trains with an attention-entropy term
 * ``GATNetHeadsChanged3LayersEmbeddingDim256Entropy`` -- models.py:1112-1148, GATConv(256, 128, heads=2)
                                                          (107 651 parameters); 256 feature columns.
 
+Six whose MLP tail normalises with ``torch.nn.LayerNorm`` like the flagship's, on the general row pass
+(``_LayerNormTail``; ``ops.ln_act_res`` / ``ops.dual_ln_act_res`` / ``ops.act``, ln_act.hip), registered in
+``LN_MODELS`` (``ALL_MODELS`` = ``MODELS`` then these); single-GPU ``hicgat.train`` only:
+
+* ``GATNetHeadsChanged4LayersReLU_LayerNorm``      -- models.py:321-377, GATConv(256, 128, heads=2),
+                                                      LayerNorm(128 / 64 / 32), relu; 256 feature columns.
+* ``GATNetHeadsChanged4LayersLeakyReLU_LayerNorm`` -- models.py:776-832, the same with leaky_relu(0.01).
+* ``GATNetHeadsChanged4LayersReLU_LayerNormEmbed512`` -- models.py:379-435, LayerNorm(256 / 128 / 64).
+* ``GATNetSelectiveResiduals``                     -- models.py:528-612, three residual blocks.
+* ``GATNetHeadsChanged4LayersReLU_LayerNormEmbed512WithResiduals`` -- models.py:437-526, ``conv1`` with
+                                                      LayerNorm(512) and a residual of its own.
+* ``GATNetSelectiveResidualsUpdatedLayerNorm``     -- models.py:693-773, gelu and a LayerNorm after each
+                                                      residual add.
+
 As in the reference, ``get_model`` never drops and ``forward`` / ``loss`` drop iff ``self.training``.
 The masks are not torch's: they are a counter-based function of (seed, step, site, row, column)
 (DESIGN.md "Feature dropout"), so a captured step replays them.  ``GATNetReduced`` still refuses to
@@ -477,6 +491,169 @@ class Net(_CoordsModel):
         return _lin(self.dense3, x)
 
 
+class _LayerNormTail(_CoordsModel):
+    """The zoo's other LayerNorm tails: conv -> act, then stages ``(dense, norm, align, norm_residual)``
+    (``stages``: attribute names, ``None`` where a stage has no residual Linear / second norm), each one
+    ``norm_residual(act(norm(dense(x))) + align(x))`` as one GEMM (two Linears: over [W; W_align]) and one
+    row pass (``ops.ln_act_res`` / ``ops.dual_ln_act_res``, ln_act.hip), then ``dense3``.  The reference's
+    ``forward`` and ``get_model`` run the same layers, so training and eval share one path."""
+
+    act = "relu"        # "relu", "leaky_relu" (slope 0.01) or "gelu", after the conv and after every norm
+    stages = ()
+    fused_tail = False  # not the flagship's tail: no one-kernel form, no weight pack in the step's first launch
+
+    def flat_parameters(self):
+        """``parameters()`` with each residual pair's weights, then its biases, adjacent (the dual-Linear
+        backward's [dW; dW_align] and [db; db_align] are then one GEMM into FlatAdam's buffer)."""
+        out, seen = [], set()
+        pair = {id(getattr(self, d).weight): (getattr(self, d), getattr(self, a)) for d, _, a, _ in self.stages if a}
+        for p in self.parameters():
+            if id(p) in seen:
+                continue
+            group = [p]
+            if id(p) in pair:
+                lin, align = pair[id(p)]
+                group = [lin.weight, align.weight, lin.bias, align.bias]
+            out += group
+            seen.update(id(q) for q in group)
+        return out
+
+    def conv_out(self, x, edge_index):
+        """act(conv(x)): relu in the aggregation's epilogue, leaky_relu / gelu as one elementwise pass."""
+        if self.act == "relu":
+            return self.conv(x, edge_index, act="relu")
+        return ops.act(self.conv(x, edge_index), self.act)
+
+    def post_act(self, x):
+        for dense, norm, align, norm_res in self.stages:
+            n2 = getattr(self, norm_res) if norm_res else None
+            if align:
+                x = ops.dual_ln_act_res(x, getattr(self, dense), getattr(self, align), getattr(self, norm), self.act, n2)
+            else:
+                x = ops.ln_act_res(_lin(getattr(self, dense), x), getattr(self, norm), self.act, norm2=n2)
+        return _lin(self.dense3, x)
+
+    def get_model(self, x, edge_index):
+        return self.post_act(self.conv_out(x, edge_index))
+
+
+class GATNetHeadsChanged4LayersReLU_LayerNorm(_LayerNormTail):
+    """models.py:321-377: GATConv(256, 128, heads=2) -> relu -> 256-128-64-32-3 with LayerNorm -> relu after
+    the first three Linears (110 083 parameters); 256 feature columns."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(256, 128, heads=2, concat=True)
+        self.densea = Linear(256, 128)
+        self.norm_a = LayerNorm(128)
+        self.dense1 = Linear(128, 64)
+        self.norm1 = LayerNorm(64)
+        self.dense2 = Linear(64, 32)
+        self.norm2 = LayerNorm(32)
+        self.dense3 = Linear(32, 3)
+
+    stages = (("densea", "norm_a", None, None), ("dense1", "norm1", None, None), ("dense2", "norm2", None, None))
+
+
+class GATNetHeadsChanged4LayersLeakyReLU_LayerNorm(GATNetHeadsChanged4LayersReLU_LayerNorm):
+    """models.py:776-832: the same layers with F.leaky_relu (slope 0.01) in place of every relu."""
+
+    act = "leaky_relu"
+
+
+class GATNetHeadsChanged4LayersReLU_LayerNormEmbed512(_LayerNormTail):
+    """models.py:379-435: GATConv(512, 256, heads=2) -> relu -> 512-256-128-64-3 with LayerNorm -> relu after
+    the first three Linears."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 256, heads=2, concat=True)
+        self.densea = Linear(512, 256)
+        self.norm_a = LayerNorm(256)
+        self.dense1 = Linear(256, 128)
+        self.norm1 = LayerNorm(128)
+        self.dense2 = Linear(128, 64)
+        self.norm2 = LayerNorm(64)
+        self.dense3 = Linear(64, 3)
+
+    stages = (("densea", "norm_a", None, None), ("dense1", "norm1", None, None), ("dense2", "norm2", None, None))
+
+
+class GATNetHeadsChanged4LayersReLU_LayerNormEmbed512WithResiduals(_LayerNormTail):
+    """models.py:437-526: the conv is registered as ``conv1`` and is itself a residual block,
+    relu(LayerNorm(512)(conv1(x))) + align1(x) on the raw features; then three residual blocks
+    relu(norm(dense(x))) + align(x) and dense3."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv1 = GATConv(512, 256, heads=2, concat=True)
+        self.norm1 = LayerNorm(512)
+        self.densea = Linear(512, 256)
+        self.norm_a = LayerNorm(256)
+        self.dense1 = Linear(256, 128)
+        self.norm1_2 = LayerNorm(128)
+        self.dense2 = Linear(128, 64)
+        self.norm2 = LayerNorm(64)
+        self.dense3 = Linear(64, 3)
+        self.align1 = Linear(512, 512)
+        self.align_a = Linear(512, 256)
+        self.align1_2 = Linear(256, 128)
+        self.align2 = Linear(128, 64)
+
+    stages = (("densea", "norm_a", "align_a", None), ("dense1", "norm1_2", "align1_2", None),
+              ("dense2", "norm2", "align2", None))
+
+    def conv_out(self, x, edge_index):
+        return ops.ln_act_res(self.conv1(x, edge_index), self.norm1, "relu", res=_lin(self.align1, x))
+
+
+class GATNetSelectiveResiduals(_LayerNormTail):
+    """models.py:528-612: the flagship's predecessor -- GATConv(512, 256, heads=2) -> relu, then THREE
+    residual blocks relu(norm(dense(x))) + align_dense(x) (the flagship dropped the third), dense3."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 256, heads=2, concat=True)
+        self.densea = Linear(512, 256)
+        self.norm_a = LayerNorm(256)
+        self.align_densea = Linear(512, 256)
+        self.dense1 = Linear(256, 128)
+        self.norm1 = LayerNorm(128)
+        self.align_dense1 = Linear(256, 128)
+        self.dense2 = Linear(128, 64)
+        self.norm2 = LayerNorm(64)
+        self.align_dense2 = Linear(128, 64)
+        self.dense3 = Linear(64, 3)
+
+    stages = (("densea", "norm_a", "align_densea", None), ("dense1", "norm1", "align_dense1", None),
+              ("dense2", "norm2", "align_dense2", None))
+
+
+class GATNetSelectiveResidualsUpdatedLayerNorm(_LayerNormTail):
+    """models.py:693-773: the flagship's layers with F.gelu for every relu and a second LayerNorm after each
+    residual add: norm_residual(gelu(norm(dense(x))) + align_dense(x)) twice, gelu(norm2(dense2(x))),
+    dense3."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = GATConv(512, 256, heads=2, concat=True)
+        self.densea = Linear(512, 256)
+        self.norm_a = LayerNorm(256)
+        self.align_densea = Linear(512, 256)
+        self.norm_residual_a = LayerNorm(256)
+        self.dense1 = Linear(256, 128)
+        self.norm1 = LayerNorm(128)
+        self.align_dense1 = Linear(256, 128)
+        self.norm_residual_1 = LayerNorm(128)
+        self.dense2 = Linear(128, 64)
+        self.norm2 = LayerNorm(64)
+        self.dense3 = Linear(64, 3)
+
+    act = "gelu"
+    stages = (("densea", "norm_a", "align_densea", "norm_residual_a"),
+              ("dense1", "norm1", "align_dense1", "norm_residual_1"), ("dense2", "norm2", None, None))
+
+
 MODELS = {
     "GATNetSelectiveResidualsUpdated": GATNetSelectiveResidualsUpdated,
     "GATNetHeadsChanged3LayersLeakyReLUv2": GATNetHeadsChanged3LayersLeakyReLUv2,
@@ -491,3 +668,20 @@ MODELS = {
     "GATNetHeadsChanged4LayersLeakyReLUHeads4": GATNetHeadsChanged4LayersLeakyReLUHeads4,
     "GATNetHeadsChanged3LayersEmbeddingDim256Entropy": GATNetHeadsChanged3LayersEmbeddingDim256Entropy,
 }
+
+# the LayerNorm tails on the general row pass (ln_act.hip); single-GPU hicgat.train only
+LN_MODELS = {
+    "GATNetHeadsChanged4LayersReLU_LayerNorm": GATNetHeadsChanged4LayersReLU_LayerNorm,
+    "GATNetHeadsChanged4LayersLeakyReLU_LayerNorm": GATNetHeadsChanged4LayersLeakyReLU_LayerNorm,
+    "GATNetHeadsChanged4LayersReLU_LayerNormEmbed512": GATNetHeadsChanged4LayersReLU_LayerNormEmbed512,
+    "GATNetSelectiveResiduals": GATNetSelectiveResiduals,
+    "GATNetHeadsChanged4LayersReLU_LayerNormEmbed512WithResiduals":
+        GATNetHeadsChanged4LayersReLU_LayerNormEmbed512WithResiduals,
+    "GATNetSelectiveResidualsUpdatedLayerNorm": GATNetSelectiveResidualsUpdatedLayerNorm,
+}
+ALL_MODELS = {**MODELS, **LN_MODELS}
+
+
+def model_class(name):
+    """The class behind a ``--model`` name: ``MODELS`` first, then ``LN_MODELS``."""
+    return MODELS[name] if name in MODELS else LN_MODELS[name]

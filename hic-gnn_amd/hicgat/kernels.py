@@ -656,8 +656,64 @@ class HipKernels:
         _lib.check(self.lib.hicgat_ln_relu_res_bwd_params(W, P(dgamma), P(dbeta), int(accumulate), P(ws), ws.numel(),
                                                           _lib.stream(ws.device)), "hicgat_ln_relu_res_bwd_params")
 
+    # -- LayerNorm -> act (+ res) (-> LayerNorm) and the elementwise act (ln_act.hip) ---------------
+    def ln_act_workspace(self, W, second_norm, device):
+        return _lib.workspace(self.lib.hicgat_ln_act_res_workspace_bytes(int(W), int(bool(second_norm))), device)
+
+    def ln_act_res_fwd(self, y, gamma, beta, eps, act, slope, res, z, row_stats, gamma2=None, beta2=None, eps2=0.0,
+                       row_stats2=None):
+        """z = LN2(act(LN(y)) + res) (``res`` / the second norm optional); rows of y / res / z may be strided."""
+        M, W = z.shape
+        with _timed("ln_act_fwd"):
+            _lib.check(self.lib.hicgat_ln_act_res_fwd(P(y), y.stride(0), M, W, P(gamma), P(beta), float(eps), int(act),
+                                                      float(slope), P(res), 0 if res is None else res.stride(0),
+                                                      P(gamma2), P(beta2), float(eps2), P(z), z.stride(0),
+                                                      P(row_stats), P(row_stats2), _lib.stream(z.device)),
+                       "hicgat_ln_act_res_fwd")
+        return z
+
+    def ln_act_res_bwd(self, dz, y, row_stats, gamma, beta, act, slope, dy, dgamma, dbeta, res=None, gamma2=None,
+                       row_stats2=None, dgamma2=None, dbeta2=None, accumulate=False, dres=None, ws=None):
+        """All four gradients None: dy / dres only, the partials stay in ``ws`` (pass it, then
+        ``ln_act_res_bwd_params`` -- on another stream if wanted)."""
+        M, W = dz.shape
+        if ws is None:
+            ws = self.ln_act_workspace(W, gamma2 is not None, dz.device)
+        with _timed("ln_act_bwd"):
+            _lib.check(self.lib.hicgat_ln_act_res_bwd(P(dz), dz.stride(0), P(y), y.stride(0), M, W, P(row_stats),
+                                                      P(gamma), P(beta), int(act), float(slope), P(res),
+                                                      0 if res is None else res.stride(0), P(gamma2), P(row_stats2),
+                                                      P(dy), dy.stride(0), P(dres),
+                                                      0 if dres is None else dres.stride(0), P(dgamma), P(dbeta),
+                                                      P(dgamma2), P(dbeta2), int(accumulate), P(ws), ws.numel(),
+                                                      _lib.stream(dz.device)), "hicgat_ln_act_res_bwd")
+
+    def ln_act_res_bwd_params(self, W, dgamma, dbeta, dgamma2, dbeta2, ws, accumulate=False):
+        _lib.check(self.lib.hicgat_ln_act_res_bwd_params(int(W), P(dgamma), P(dbeta), P(dgamma2), P(dbeta2),
+                                                         int(accumulate), P(ws), ws.numel(), _lib.stream(ws.device)),
+                   "hicgat_ln_act_res_bwd_params")
+
+    def act_fwd(self, x, act, slope, y):
+        """y = act(x), gelu or leaky_relu, over a contiguous [M, W] tensor."""
+        M, W = x.shape
+        assert x.is_contiguous() and y.is_contiguous() and y.shape == x.shape
+        with _timed("act_fwd"):
+            _lib.check(self.lib.hicgat_act_fwd(P(x), M, W, int(act), float(slope), P(y), _lib.stream(x.device)),
+                       "hicgat_act_fwd")
+        return y
+
+    def act_bwd(self, dy, x, act, slope, dx):
+        """dx = dy * act'(x) from the saved input ``x`` (``dx`` may be ``dy``)."""
+        M, W = x.shape
+        assert x.is_contiguous() and dy.is_contiguous() and dx.is_contiguous() and dy.shape == x.shape == dx.shape
+        with _timed("act_bwd"):
+            _lib.check(self.lib.hicgat_act_bwd(P(dy), P(x), M, W, int(act), float(slope), P(dx),
+                                               _lib.stream(x.device)), "hicgat_act_bwd")
+        return dx
+
     # -- feature dropout (dropout.hip): act -> Dropout with a counter-based mask -------------------
     ACT_NONE, ACT_RELU, ACT_LEAKY_RELU = 0, 1, 2   # include/hicgat.h HICGAT_ACT_*
+    ACT_GELU = 3                                   # ln_act.hip only
 
     def act_dropout_fwd(self, x, act, slope, p, seed, step_ctr, step_value, site, row_offset, y):
         """y = kept ? act(x) * scale : 0 (``y`` may be ``x``); the step comes from the device count

@@ -472,6 +472,163 @@ def ln_relu_res(y, norm, res=None):
     return _LnReluResFn.apply(y, norm.weight, norm.bias, res, norm.eps)
 
 
+# ---- LayerNorm tails of the other zoo models (ln_act.hip): LayerNorm -> act (+ res) (-> LayerNorm) ----
+LN_WIDTHS = (32, 64, 128, 256, 512)
+
+
+def _ln_act_code(act):
+    """The activation of the LayerNorm tails and of ``ops.act``: ``None`` / "none", "relu", "leaky_relu"
+    (slope 0.01), ("leaky_relu", slope) or "gelu" (the erf form, F.gelu's default) -> (HICGAT_ACT_* code,
+    slope).  A parser of its own: the dropout and BatchNorm ops (``_act_code``) have no gelu."""
+    if isinstance(act, tuple) and len(act) == 2 and act[0] == "leaky_relu":
+        if not float(act[1]) > 0.0:
+            raise ValueError(f"leaky_relu needs a slope > 0; got {act[1]!r}")
+        return kernels.HipKernels.ACT_LEAKY_RELU, float(act[1])
+    if act in (None, "none"):
+        return kernels.HipKernels.ACT_NONE, 0.0
+    if act == "relu":
+        return kernels.HipKernels.ACT_RELU, 0.0
+    if act == "leaky_relu":
+        return kernels.HipKernels.ACT_LEAKY_RELU, 0.01
+    if act == "gelu":
+        return kernels.HipKernels.ACT_GELU, 0.0
+    raise ValueError(f"activation must be None, 'relu', 'leaky_relu', ('leaky_relu', slope) or 'gelu'; got {act!r}")
+
+
+def _ln_check(norm, what="norm"):
+    """The width of a ``torch.nn.LayerNorm`` the row pass takes; refuses everything else, by name."""
+    if not isinstance(norm, torch.nn.LayerNorm):
+        raise TypeError(f"{what} must be a torch.nn.LayerNorm; got {type(norm).__name__}")
+    if not norm.elementwise_affine or norm.weight is None or norm.bias is None:
+        raise NotImplementedError(f"{what}: LayerNorm(elementwise_affine=False) or without a bias is not implemented")
+    if len(norm.normalized_shape) != 1:
+        raise NotImplementedError(f"{what}: a {len(norm.normalized_shape)}-D normalized_shape "
+                                  f"{tuple(norm.normalized_shape)} is not implemented (rows of one width only)")
+    W = int(norm.normalized_shape[0])
+    if W not in LN_WIDTHS:
+        raise NotImplementedError(f"{what}: LayerNorm widths {LN_WIDTHS} are implemented; got {W}")
+    return W
+
+
+def _ln_pair_check(norm, norm2):
+    W = _ln_check(norm)
+    if norm2 is not None and _ln_check(norm2, "norm2") != W:
+        raise ValueError(f"norm2 must have norm's width {W}; got {int(norm2.normalized_shape[0])}")
+    return W
+
+
+def _rows_f32(t, W, what):
+    if t.dim() != 2 or t.dtype != torch.float32 or t.shape[1] != W:
+        raise ValueError(f"{what} must be a float32 [rows, {W}] tensor; got {t.dtype} {tuple(t.shape)}")
+
+
+def _ln_act_bwd(K, cfg, params, dz, y, stats, res, stats2, dy, dres=None):
+    """The row pass of the backward and its parameter sums, which go where ``_ln_bwd``'s go: without every
+    sink into new tensors (returned); with them and nothing overlapping straight into the sinks; while
+    overlapping into a workspace as partials, and adding those to the sinks is queued side work.  Returns
+    (dgamma, dbeta, dgamma2, dbeta2) for autograd."""
+    code, slope = cfg
+    gamma, beta, gamma2, beta2 = params
+    n2 = gamma2 is not None
+    kw = dict(res=res if n2 else None, gamma2=gamma2, row_stats2=stats2, dres=dres)
+    sinks = [_sink(p) for p in ((gamma, beta, gamma2, beta2) if n2 else (gamma, beta))]
+    if any(s is None for s in sinks):
+        dg, db = torch.empty_like(gamma), torch.empty_like(beta)
+        dg2, db2 = (torch.empty_like(gamma2), torch.empty_like(beta2)) if n2 else (None, None)
+        K.ln_act_res_bwd(dz, y, stats, gamma, beta, code, slope, dy, dg, db, dgamma2=dg2, dbeta2=db2, **kw)
+        return dg, db, dg2, db2
+    sinks += [None, None] if not n2 else []
+    if not paramgrads.overlapping():
+        K.ln_act_res_bwd(dz, y, stats, gamma, beta, code, slope, dy, sinks[0], sinks[1], dgamma2=sinks[2],
+                         dbeta2=sinks[3], accumulate=True, **kw)
+    else:
+        W = y.shape[1]
+        ws = K.ln_act_workspace(W, n2, y.device)
+        K.ln_act_res_bwd(dz, y, stats, gamma, beta, code, slope, dy, None, None, ws=ws, **kw)
+        param_launch(lambda: K.ln_act_res_bwd_params(W, *sinks, ws, accumulate=True), ws)
+    return None, None, None, None
+
+
+class _LnActResFn(torch.autograd.Function):
+    """LN2(act(LN(y)) + res) in one pass (ln_act.hip); ``res`` and the second norm are optional."""
+
+    @staticmethod
+    def forward(ctx, y, res, gamma, beta, gamma2, beta2, eps, eps2, code, slope):
+        K = kernels.default()
+        M, W = y.shape
+        n2 = gamma2 is not None
+        z = torch.empty((M, W), dtype=torch.float32, device=y.device)
+        stats = torch.empty((M, 2), dtype=torch.float32, device=y.device)
+        stats2 = torch.empty((M, 2), dtype=torch.float32, device=y.device) if n2 else None
+        K.ln_act_res_fwd(y, gamma, beta, eps, code, slope, res, z, stats, gamma2, beta2, eps2, stats2)
+        ctx.save_for_backward(y, stats, res if n2 else None, stats2)
+        ctx.has_res = res is not None
+        ctx.cfg = (code, slope)
+        ctx.params = (gamma, beta, gamma2, beta2)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        K = kernels.default()
+        y, stats, res, stats2 = ctx.saved_tensors
+        n2 = ctx.params[2] is not None
+        dz = dz.contiguous()
+        dy = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+        # without the second norm d(res) is dz itself; with it the kernel writes du
+        dres = torch.empty_like(dy) if (ctx.has_res and n2) else None
+        dg, db, dg2, db2 = _ln_act_bwd(K, ctx.cfg, ctx.params, dz, y, stats, res, stats2, dy, dres)
+        return dy, ((dres if n2 else dz) if ctx.has_res else None), dg, db, dg2, db2, None, None, None, None
+
+
+def ln_act_res(y, norm, act, res=None, norm2=None):
+    """``norm2(act(norm(y)) + res)`` for ``torch.nn.LayerNorm``s of one width in ``LN_WIDTHS`` (``res`` and
+    ``norm2`` optional), as one row pass forward and one backward.  ``act``: None, "relu", "leaky_relu",
+    ("leaky_relu", slope) or "gelu"."""
+    W = _ln_pair_check(norm, norm2)
+    code, slope = _ln_act_code(act)
+    _rows_f32(y, W, "y")
+    if res is not None:
+        _rows_f32(res, W, "res")
+        if res.shape != y.shape:
+            raise ValueError(f"res must have y's shape {tuple(y.shape)}; got {tuple(res.shape)}")
+    _dev_check(y, res)
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    if res is not None and res.stride(1) != 1:
+        res = res.contiguous()
+    g2, b2, e2 = (norm2.weight, norm2.bias, norm2.eps) if norm2 is not None else (None, None, 0.0)
+    return _LnActResFn.apply(y, res, norm.weight, norm.bias, g2, b2, norm.eps, e2, code, slope)
+
+
+class _ActFn(torch.autograd.Function):
+    """Elementwise gelu / leaky_relu (ln_act.hip); the backward reads the saved input."""
+
+    @staticmethod
+    def forward(ctx, x, code, slope):
+        x = x.contiguous()
+        y = kernels.default().act_fwd(x, code, slope, torch.empty_like(x))
+        ctx.save_for_backward(x)
+        ctx.cfg = (code, slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        return kernels.default().act_bwd(dy.contiguous(), x, *ctx.cfg, torch.empty_like(x)), None, None
+
+
+def act(x, act):
+    """F.gelu(x) ("gelu", the erf form) or F.leaky_relu(x, slope) ("leaky_relu", ("leaky_relu", slope)) of a
+    float32 [rows, W] device tensor, W % 4 == 0, as one launch each way."""
+    code, slope = _ln_act_code(act)
+    if code not in (kernels.HipKernels.ACT_GELU, kernels.HipKernels.ACT_LEAKY_RELU):
+        raise ValueError(f"ops.act runs 'gelu' and 'leaky_relu'; got {act!r} (relu runs in the GATConv's epilogue)")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] % 4:
+        raise ValueError(f"ops.act needs a float32 [rows, W] tensor with W % 4 == 0; got {x.dtype} {tuple(x.shape)}")
+    _dev_check(x)
+    return _ActFn.apply(x, code, slope)
+
+
 class _BnActDropoutFn(torch.autograd.Function):
     """BatchNorm1d -> act -> Dropout(p) (batchnorm.hip; models.py:288-291).  A training-mode forward
     takes the batch statistics (two launches), updates the module's buffers on the device and applies
@@ -686,6 +843,67 @@ def dual_ln_relu_res(x, lin1, lin2, norm):
                                   norm.eps)
 
 
+class _DualLnActResFn(torch.autograd.Function):
+    """norm2(act(norm(lin1(x))) + lin2(x)) -- the residual blocks of models.py:437-526, :528-612 and
+    :693-773 -- as ``_DualLnReluResFn`` does it: ONE GEMM Y = x [W1; W2]^T + [b1; b2], one row pass over
+    Y = [y | res] (ln_act.hip), a packed dY = [dy | dres] from the backward's row pass, so dx is ONE GEMM
+    and, with the pairs adjacent in FlatAdam's buffer, dW and db one GEMM."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, gamma2, beta2, eps, eps2, code, slope):
+        K = kernels.default()
+        x = x.contiguous()
+        M = x.shape[0]
+        w = W1.shape[0]
+        n2 = gamma2 is not None
+        Y = torch.empty((M, 2 * w), dtype=torch.float32, device=x.device)
+        K.gemm(0, 0, M, 2 * w, x.shape[1], x, _joined(W1, W2).contiguous(), Y, bias=_joined(b1, b2).contiguous(),
+               name="gemm_fwd")
+        z = torch.empty((M, w), dtype=torch.float32, device=x.device)
+        stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+        stats2 = torch.empty((M, 2), dtype=torch.float32, device=x.device) if n2 else None
+        K.ln_act_res_fwd(Y[:, :w], gamma, beta, eps, code, slope, Y[:, w:], z, stats, gamma2, beta2, eps2, stats2)
+        ctx.save_for_backward(x, Y, stats, stats2)
+        ctx.cfg = (code, slope)
+        ctx.params = (W1, b1, W2, b2, gamma, beta, gamma2, beta2)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        K = kernels.default()
+        x, Y, stats, stats2 = ctx.saved_tensors
+        W1, b1, W2, b2 = ctx.params[:4]
+        dz = dz.contiguous()
+        M, w = dz.shape
+        dY = torch.empty((M, 2 * w), dtype=torch.float32, device=dz.device)
+        dg, db, dg2, db2 = _ln_act_bwd(K, ctx.cfg, ctx.params[4:], dz, Y[:, :w], stats, Y[:, w:], stats2, dY[:, :w],
+                                       dres=dY[:, w:])
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.gemm(0, 1, M, x.shape[1], 2 * w, dY, _joined(W1, W2).contiguous(), torch.empty_like(x),
+                        name="gemm_dx")
+        dW1, db1, dW2, db2_ = _dual_param_grads(K, W1, b1, W2, b2, dY, x)
+        return dx, dW1, db1, dW2, db2_, dg, db, dg2, db2, None, None, None, None
+
+
+def dual_ln_act_res(x, lin1, lin2, norm, act, norm2=None):
+    """``norm2(act(norm(lin1(x))) + lin2(x))`` (``norm2`` optional) on the fused kernels: one GEMM over
+    [W1; W2], one row pass.  ``act`` as ``ln_act_res``."""
+    W = _ln_pair_check(norm, norm2)
+    code, slope = _ln_act_code(act)
+    for lin, what in ((lin1, "lin1"), (lin2, "lin2")):
+        if not isinstance(lin, torch.nn.Linear) or lin.bias is None or lin.out_features != W:
+            raise ValueError(f"{what} must be a torch.nn.Linear with a bias and {W} outputs (the norm's width)")
+    if lin1.in_features != lin2.in_features:
+        raise ValueError("lin1 and lin2 must read the same input width")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] != lin1.in_features:
+        raise ValueError(f"x must be a float32 [rows, {lin1.in_features}] tensor; got {x.dtype} {tuple(x.shape)}")
+    _dev_check(x)
+    g2, b2, e2 = (norm2.weight, norm2.bias, norm2.eps) if norm2 is not None else (None, None, 0.0)
+    return _DualLnActResFn.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, norm.weight, norm.bias, g2, b2,
+                                 norm.eps, e2, code, slope)
+
+
 # The flagship's MLP tail forward as ONE launch (tail_fused.hip) for row counts in [MIN_M, MAX_M]
 # (HICGAT_FUSED_TAIL=0: off).  Measured (profiles/r03r_ab_fused_tail.txt, 4-deep weight prefetch):
 # a rank's shard at P = 8 (2 700 rows) 0.613 vs 0.650 ms per rank step, P = 4 (5 000) 0.877 vs
@@ -799,7 +1017,8 @@ class _FusedTailFn(torch.autograd.Function):
 
 
 def fused_tail_ok(model, x):
-    return (FUSED_TAIL and x.is_cuda and x.dim() == 2 and FUSED_TAIL_MIN_M <= x.shape[0] <= FUSED_TAIL_MAX_M
+    return (FUSED_TAIL and getattr(model, "fused_tail", True)
+            and x.is_cuda and x.dim() == 2 and FUSED_TAIL_MIN_M <= x.shape[0] <= FUSED_TAIL_MAX_M
             and x.shape[1] == 512
             and x.dtype == torch.float32 and x.stride(1) == 1
             and model.norm_a.eps == model.norm1.eps == model.norm2.eps)
@@ -848,6 +1067,7 @@ def step_pack(model, x):
     head-fused tail's third weight)."""
     m = model
     if not (STEP_PACK and TAIL_PACK and FUSED_TAIL and x.is_cuda and hasattr(m, "align_densea") and hasattr(m, "norm_a")
+            and getattr(m, "fused_tail", True)      # gat_models._LayerNormTail has these names and another tail
             and FUSED_TAIL_MIN_M <= x.shape[0] <= FUSED_TAIL_MAX_M
             and m.norm_a.eps == m.norm1.eps == m.norm2.eps):
         return None

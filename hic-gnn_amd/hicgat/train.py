@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import graph, metrics, ops
-from .gat_models import MODELS
+from .gat_models import ALL_MODELS, MODELS, model_class  # noqa: F401
 from .optim import FlatAdam
 
 
@@ -151,7 +151,7 @@ def make_parser():
     p.add_argument("-lr", "--learningrate", type=float, default=1e-3)
     p.add_argument("-th", "--threshold", type=float, default=1e-8)
     p.add_argument("--steps", type=int, default=None, help="fixed step count instead of the threshold rule")
-    p.add_argument("--model", default="GATNetSelectiveResidualsUpdated", choices=sorted(MODELS))
+    p.add_argument("--model", default="GATNetSelectiveResidualsUpdated", choices=sorted(ALL_MODELS))
     p.add_argument("--loss", default="mse", choices=list(LOSSES))
     p.add_argument("--alpha", type=float, default=1.0, help="weight of the (1 - dSCC) term of --loss mse+dscc "
                                                             "(combined_loss_training.py:142)")
@@ -193,7 +193,7 @@ def main(argv=None):
     runs = []
     for f in conv:
         print(f"Training model using conversion value {f}.")
-        model = MODELS[a.model]().to(data.x.device)
+        model = model_class(a.model)().to(data.x.device)
         extra = {"alpha": a.alpha} if a.loss == "mse+dscc" else {}
         _, hist = train(model, data, truth, a.learningrate, a.threshold, a.steps, a.loss, **extra)
         coords = model.get_model(data.x.float(), data.edge_index).detach()

@@ -474,6 +474,53 @@ size_t hicgat_ln_relu_res_workspace_bytes(int W);
 int hicgat_ln_relu_res_bwd_params(int W, float *dgamma, float *dbeta, int accumulate, void *workspace,
                                   size_t workspace_bytes, hicgat_stream_t stream);
 
+/* ---- LayerNorm tails of the other zoo models (ln_act.hip; models.py:321-377, :379-435, :437-526,
+ * :528-612, :693-773, :776-832): LayerNorm -> activation (+ residual) (-> a second LayerNorm) as one
+ * row pass:
+ *   u = act(LayerNorm(y; gamma, beta, eps)) + res            (res may be NULL)
+ *   z = LayerNorm(u; gamma2, beta2, eps2)                    (gamma2 != NULL; else z = u)
+ * torch.nn.LayerNorm semantics (biased variance about the mean, eps inside the square root).  act is a
+ * HICGAT_ACT_* code: none, relu, leaky_relu (x > 0 ? x : x * slope) or gelu = 0.5 x (1 + erf(x / sqrt 2))
+ * (F.gelu's default, not the tanh form).  W in {32, 64, 128, 256, 512}.  y / res / z rows are ldy / ldr /
+ * ldz floats apart (column slices of one [M, 2W] buffer pass ld = 2W).  row_stats [M, 2] = (mean, rstd)
+ * and, with the second norm, row_stats2 [M, 2] = (mean2, rstd2) are saved for the backward.  With relu and
+ * no second norm the results are hicgat_ln_relu_res_fwd / _bwd's, bit for bit.
+ * Backward (recomputes pre = yhat gamma + beta, and u from y and res with the second norm: pass the
+ * forward's res, gamma2 and row_stats2 then; res is not read otherwise):
+ *   du = rstd2 (dz gamma2 - mean(.) - uhat mean(. uhat)), or dz without the second norm;
+ *   dres = du, written to dres (ld lddres) when dres != NULL, e.g. beside dy in a packed [dy | dres] row;
+ *   g = du act'(pre): relu [pre > 0], leaky_relu (pre > 0 ? 1 : slope), gelu Phi(pre) + pre phi(pre);
+ *   dy (ld lddy) = rstd (g gamma - mean(.) - yhat mean(. yhat));
+ *   dgamma = sum g yhat, dbeta = sum g, dgamma2 = sum dz uhat, dbeta2 = sum dz over the rows: per-wave
+ *   partials in the workspace, then fixed-order column sums (deterministic, no atomics); accumulate != 0
+ *   adds into them.  dgamma = dbeta = dgamma2 = dbeta2 = NULL: the partials stay in the workspace and
+ *   hicgat_ln_act_res_bwd_params (dgamma2 / dbeta2 given iff the backward had the second norm) reduces
+ *   them, e.g. on another stream after an event -- the same bits as the one-call form.
+ * Unknown W or act: HICGAT_EUNSUPPORTED.  A NULL pointer, M < 0, eps <= 0, an ld < W, leaky_relu with
+ * slope <= 0, gamma2 without beta2 (or dgamma without dbeta, ...), a small workspace: HICGAT_EINVAL;
+ * all of it is checked before any launch.  M == 0: the forward returns HICGAT_OK without a launch (the
+ * backward still zeroes or keeps the parameter gradients).
+ * workspace: hicgat_ln_act_res_workspace_bytes(W, second_norm) (0 for an unsupported W). */
+int hicgat_ln_act_res_fwd(const float *y, int64_t ldy, int M, int W, const float *gamma, const float *beta, float eps,
+                          int act, float slope, const float *res, int64_t ldr, const float *gamma2, const float *beta2,
+                          float eps2, float *z, int64_t ldz, float *row_stats, float *row_stats2,
+                          hicgat_stream_t stream);
+int hicgat_ln_act_res_bwd(const float *dz, int64_t lddz, const float *y, int64_t ldy, int M, int W,
+                          const float *row_stats, const float *gamma, const float *beta, int act, float slope,
+                          const float *res, int64_t ldr, const float *gamma2, const float *row_stats2, float *dy,
+                          int64_t lddy, float *dres, int64_t lddres, float *dgamma, float *dbeta, float *dgamma2,
+                          float *dbeta2, int accumulate, void *workspace, size_t workspace_bytes,
+                          hicgat_stream_t stream);
+int hicgat_ln_act_res_bwd_params(int W, float *dgamma, float *dbeta, float *dgamma2, float *dbeta2, int accumulate,
+                                 void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
+size_t hicgat_ln_act_res_workspace_bytes(int W, int second_norm);
+/* Elementwise y = act(x) over a contiguous [M, W] tensor (the F.gelu / F.leaky_relu that follows the
+ * GATConv at models.py:717 / :795), act = HICGAT_ACT_GELU or HICGAT_ACT_LEAKY_RELU (others, or W % 4 != 0:
+ * HICGAT_EUNSUPPORTED), 16-B aligned (float4 loads); the backward dx = dy act'(x) reads the saved INPUT x. */
+int hicgat_act_fwd(const float *x, int M, int W, int act, float slope, float *y, hicgat_stream_t stream);
+int hicgat_act_bwd(const float *dy, const float *x, int M, int W, int act, float slope, float *dx,
+                   hicgat_stream_t stream);
+
 /* ---- The flagship's MLP tail forward in one launch (tail_fused.hip; replaces the dual-Linear GEMMs,
  * ln_relu_res passes and Linear GEMMs of models.py:637-659 for GATNetSelectiveResidualsUpdated) ----
  * x [M][512] (ld ldx, 16-B aligned rows): the GATConv output after its relu.  W1c [512][512] = [W_densea;
@@ -643,7 +690,8 @@ int hicgat_step_begin_pack(float *grad, int64_t n, int64_t *step_counter, const 
  * hicgat_dropout_advance increments), else step_value.  W % 4 == 0 and every ld a multiple of 4
  * (else HICGAT_EUNSUPPORTED), x / y / dy / dx 16-B aligned, step_counter 8-B aligned, mask 4-B
  * aligned (else HICGAT_EINVAL); all of it checked before any launch.  M = 0 is a no-op. */
-enum { HICGAT_ACT_NONE = 0, HICGAT_ACT_RELU = 1, HICGAT_ACT_LEAKY_RELU = 2 };
+enum { HICGAT_ACT_NONE = 0, HICGAT_ACT_RELU = 1, HICGAT_ACT_LEAKY_RELU = 2,
+       HICGAT_ACT_GELU = 3 /* hicgat_ln_act_res_* and hicgat_act_* only; HICGAT_EINVAL elsewhere */ };
 /* y[r][c] = kept ? act(x[r][c]) * scale : 0;  relu(x) = x <= 0 ? 0 : x,  leaky_relu(x) = x > 0 ? x :
  * x * slope (fp32).  In place (y == x, ldy == ldx) is allowed. */
 int hicgat_act_dropout_fwd(const float *x, int64_t ldx, int M, int W, int act, float slope, double p, uint64_t seed,
