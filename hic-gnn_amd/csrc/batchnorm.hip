@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double *__restri
 }
 
 // The constants of one column: stats [4, W] (training) or the running buffers (eval: rstd =
-// 1 / sqrt(running_var + eps), correctly rounded square root as in layernorm.hip).
+// 1 / sqrt(running_var + eps), correctly rounded square root as in ln_act.hip).
 struct Col {
   float mean, lo, rstd, rstd_lo;
 };

@@ -14,8 +14,8 @@
 //             dbeta += g;  dy = rstd (g gamma - mean(.) - yhat mean(. yhat)).
 // act: none, relu, leaky_relu(slope), gelu = 0.5 x (1 + erf(x / sqrt 2)) (F.gelu's default, erff);
 // gelu' = Phi(x) + x phi(x).
-// Lane layout, W >= 64: one wave per row, column q * 64 + lane (layernorm.hip's; with relu and no
-// second norm the arithmetic is that file's, operation for operation, so the results are its bits).
+// Lane layout, W >= 64: one wave per row, column q * 64 + lane.  With relu and no second norm this is the
+// flagship's row pass (models.py:641-655), whose bits tests/golden/ln_row_pass_bits.json pins.
 // W = 32: two rows per wave -- lanes 0..31 hold row 2k, lanes 32..63 row 2k + 1, sums over the half
 // wave -- so every wave load is a full 256 B and half as many waves run; the half wave whose row is
 // past M loads and stores nothing (it feeds zeros to its own half's sums only).
@@ -26,7 +26,7 @@
 
 namespace hicgat {
 
-constexpr int kLnActWaves = 4096;   // waves of the backward grid, as layernorm.hip's kLnWaves
+constexpr int kLnActWaves = 4096;   // waves of the backward grid (partials: kLnActWaves x 2 or 4 x W; 4 blocks per CU)
 
 template <int W>
 struct RowLanes {

@@ -18,16 +18,14 @@
 // ds_read_b128 of the activations (LDS) and a global float4 of the weight row (L2) -- and the
 // weights of group g + 4 are loaded right after group g's MFMAs.  C/D: col = l & 15, row = 4(l >> 4)
 // + r.  The k order is fixed (deterministic); it differs from the tiled GEMMs' by fp32 rounding.
-// LayerNorm: one wave per row, the arithmetic of ln_relu_res_fwd_kernel (layernorm.hip) on the row
-// held in LDS (torch.nn.LayerNorm: biased variance, eps 1e-5 inside the square root).
+// LayerNorm: one wave per row, the arithmetic of ln_act_res_fwd_kernel (ln_act.hip, relu, no second
+// norm) on the row held in LDS (torch.nn.LayerNorm: biased variance, eps 1e-5 inside the square root).
 #include "common.hpp"
 #include "pack.hpp"
 
 #include <algorithm>
 #include <mutex>
 #include <unordered_map>
-
-extern "C" size_t hicgat_ln_relu_res_workspace_bytes(int W);   // layernorm.hip
 
 namespace hicgat {
 
@@ -432,11 +430,11 @@ __device__ __forceinline__ void put_tiles(const f32x4 (&acc)[RB / 16][NT], int n
   }
 }
 
-// LayerNorm + ReLU (+ residual) backward of rows wv, wv + 4, ... (ln_relu_res_bwd_kernel's
-// arithmetic): dz from LDS (Dz, stride ldd), y / stats from global; dy (and dres = dz beside it when
-// RES) into LDS (Gs, stride lds: [dy | dres]) and the global dY rows ([M][W or 2W]); the wave's
-// dgamma / dbeta partials, summed over the workgroup's waves, into row ``slot`` of part ([slots][2][W],
-// hicgat_ln_relu_res_bwd_params).
+// LayerNorm + ReLU (+ residual) backward of rows wv, wv + 4, ... (the arithmetic of ln_act.hip's
+// ln_act_res_bwd_kernel with relu and no second norm): dz from LDS (Dz, stride ldd), y / stats from
+// global; dy (and dres = dz beside it when RES) into LDS (Gs, stride lds: [dy | dres]) and the global
+// dY rows ([M][W or 2W]); the wave's dgamma / dbeta partials, summed over the workgroup's waves, into
+// row ``slot`` of part ([slots][2][W], which hicgat_colsum then sums over the slots).
 template <int RB, int W, bool RES, int NW = 4>
 __device__ __forceinline__ void ln_bwd_rows(const float *__restrict__ Dz, int ldd, const float *__restrict__ y,
                                             int64_t ldy, const float2 *__restrict__ stats,

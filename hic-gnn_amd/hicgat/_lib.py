@@ -112,11 +112,6 @@ SIGNATURES = {
     "hicgat_param_grads_grouped": (c_int, [c_wjobs, c_int, c_cjobs, c_int, c_int, c_p, c_sz, c_p]),
     "hicgat_colsum": (c_int, [c_p, c_i64, c_int, c_int, c_p, c_int, c_p, c_sz, c_p]),
     "hicgat_colsum_workspace_bytes": (c_sz, [c_int, c_int]),
-    "hicgat_ln_relu_res_fwd": (c_int, [c_p, c_i64, c_int, c_int, c_p, c_p, c_f, c_p, c_i64, c_p, c_p, c_p]),
-    "hicgat_ln_relu_res_bwd": (c_int, [c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p,
-                                       c_p, c_int, c_p, c_sz, c_p]),
-    "hicgat_ln_relu_res_workspace_bytes": (c_sz, [c_int]),
-    "hicgat_ln_relu_res_bwd_params": (c_int, [c_int, c_p, c_p, c_int, c_p, c_sz, c_p]),
     "hicgat_ln_act_res_fwd": (c_int, [c_p, c_i64, c_int, c_int, c_p, c_p, c_f, c_int, c_f, c_p, c_i64, c_p, c_p, c_f,
                                       c_p, c_i64, c_p, c_p, c_p]),
     "hicgat_ln_act_res_bwd": (c_int, [c_p, c_i64, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_int, c_f, c_p, c_i64,

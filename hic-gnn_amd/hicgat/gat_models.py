@@ -29,7 +29,7 @@ One that returns its attention weights and trains with an attention-entropy term
 * ``GATNetHeadsChanged3LayersEmbeddingDim256Entropy`` -- models.py:1112-1148, GATConv(256, 128, heads=2)
                                                          (107 651 parameters); 256 feature columns.
 
-Six whose MLP tail normalises with ``torch.nn.LayerNorm`` like the flagship's, on the general row pass
+Six whose MLP tail normalises with ``torch.nn.LayerNorm`` like the flagship's, on the same row pass
 (``_LayerNormTail``; ``ops.ln_act_res`` / ``ops.dual_ln_act_res`` / ``ops.act``, ln_act.hip), registered in
 ``LN_MODELS`` (``ALL_MODELS`` = ``MODELS`` then these); single-GPU ``hicgat.train`` only:
 
@@ -115,9 +115,9 @@ class GATNetSelectiveResidualsUpdated(_CoordsModel):
         is one kernel (ops.fused_tail, tail_fused.hip) with the same backward."""
         if ops.fused_tail_ok(self, x):
             return ops.fused_tail(self, x)
-        x = ops.dual_ln_relu_res(x, self.densea, self.align_densea, self.norm_a)
-        x = ops.dual_ln_relu_res(x, self.dense1, self.align_dense1, self.norm1)
-        x = ops.ln_relu_res(_lin(self.dense2, x), self.norm2)
+        x = ops.dual_ln_act_res(x, self.densea, self.align_densea, self.norm_a, "relu")
+        x = ops.dual_ln_act_res(x, self.dense1, self.align_dense1, self.norm1, "relu")
+        x = ops.ln_act_res(_lin(self.dense2, x), self.norm2, "relu")
         return _lin(self.dense3, x)
 
     def tail(self, x):

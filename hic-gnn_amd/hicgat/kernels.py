@@ -533,24 +533,6 @@ class HipKernels:
                                               _lib.stream(A.device)), "hicgat_colsum")
         return out
 
-    def ln_relu_res_fwd(self, y, gamma, beta, eps, res, z, row_stats):
-        M, W = z.shape
-        _lib.check(self.lib.hicgat_ln_relu_res_fwd(P(y), y.stride(0), M, W, P(gamma), P(beta), float(eps), P(res),
-                                                   0 if res is None else res.stride(0), P(z), P(row_stats),
-                                                   _lib.stream(z.device)), "hicgat_ln_relu_res_fwd")
-
-    def ln_relu_res_bwd(self, dz, y, row_stats, gamma, beta, dy, dgamma, dbeta, accumulate=False, dres=None,
-                        ws=None):
-        """dgamma = dbeta = None: dy / dres only, the partials stay in ``ws`` (pass it, then
-        ``ln_relu_res_bwd_params(W, dgamma, dbeta, ws)`` -- on another stream if wanted)."""
-        M, W = dz.shape
-        if ws is None:
-            ws = self.ln_workspace(W, dz.device)
-        _lib.check(self.lib.hicgat_ln_relu_res_bwd(P(dz), P(y), y.stride(0), M, W, P(row_stats), P(gamma), P(beta),
-                                                   P(dy), dy.stride(0), P(dres), 0 if dres is None else dres.stride(0),
-                                                   P(dgamma), P(dbeta), int(accumulate), P(ws), ws.numel(),
-                                                   _lib.stream(dz.device)), "hicgat_ln_relu_res_bwd")
-
     def tail_pack(self, W1c, W2c, Wh=None):
         """The packed copies of W1c [512, 512], W2c [256, 256] and (head forms) Wh [512, 512] that the
         tail kernels read instead of the row-major weights (hicgat_tail_pack): a new device buffer, so
@@ -603,7 +585,7 @@ class HipKernels:
                        rows=None):
         """The tail's input-gradient chain in one launch (tail_fused.hip): returns (dx, dY1, dY2, dy3,
         (ws1, ws2, ws3)) -- the LayerNorm dgamma/dbeta partials stay in the workspaces
-        (``ln_relu_res_bwd_params``).  ``heads``: the head-fused form (dx None; the xagg GATConv's
+        (``ops._ln_param_grads`` sums them).  ``heads``: the head-fused form (dx None; the xagg GATConv's
         dout, delta and dxa written into the ``ops.TailHeads`` buffers instead).  ``rows`` = (act, y,
         out2, bias, row_stats, dout): the single-GPU GATConv's rows pass in the epilogue
         (hicgat_tail_bwd_fused_rows; dx None, dout and row_stats[:, 4:8] written instead)."""
@@ -648,13 +630,6 @@ class HipKernels:
     def tail_partial_rows(self, M):
         """Rows of LayerNorm partials hicgat_tail_bwd_fused leaves per workspace: one per workgroup."""
         return -(-M // 16)
-
-    def ln_workspace(self, W, device):
-        return _lib.workspace(self.lib.hicgat_ln_relu_res_workspace_bytes(W), device)
-
-    def ln_relu_res_bwd_params(self, W, dgamma, dbeta, ws, accumulate=False):
-        _lib.check(self.lib.hicgat_ln_relu_res_bwd_params(W, P(dgamma), P(dbeta), int(accumulate), P(ws), ws.numel(),
-                                                          _lib.stream(ws.device)), "hicgat_ln_relu_res_bwd_params")
 
     # -- LayerNorm -> act (+ res) (-> LayerNorm) and the elementwise act (ln_act.hip) ---------------
     def ln_act_workspace(self, W, second_norm, device):

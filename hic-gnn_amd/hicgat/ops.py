@@ -280,17 +280,20 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        K = kernels.default()
-        x, W = ctx.saved_tensors
-        dy = dy.contiguous()
-        M = x.shape[0]
-        n_out, n_in = W.shape
-        dx = dW = db = None
-        if ctx.needs_input_grad[0]:
-            dx = K.gemm(0, 1, M, n_in, n_out, dy, W.contiguous(), torch.empty_like(x), name="gemm_dx")
-        dW, db = _wb_grad_to(K, ctx.params[0], ctx.params[1], dy, x, need_w=ctx.needs_input_grad[1],
-                             need_b=ctx.has_bias and ctx.needs_input_grad[2])
-        return dx, dW, db
+        x, _ = ctx.saved_tensors
+        need_dx, need_w, need_b = ctx.needs_input_grad
+        return _linear_backward(*ctx.params, x, dy, need_dx, need_w, ctx.has_bias and need_b)
+
+
+def _linear_backward(W, b, x, dy, need_dx=True, need_w=True, need_b=True):
+    """``_LinearFn``'s backward on its operands: (dx, dW, db)."""
+    K = kernels.default()
+    dy = dy.contiguous()
+    n_out, n_in = W.shape
+    dx = None
+    if need_dx:
+        dx = K.gemm(0, 1, x.shape[0], n_in, n_out, dy, W.contiguous(), torch.empty_like(x), name="gemm_dx")
+    return (dx,) + _wb_grad_to(K, W, b, dy, x, need_w=need_w, need_b=need_b)
 
 
 def linear(x, W, b=None):
@@ -417,62 +420,8 @@ def dual_linear(x, lin1, lin2):
     return _DualLinearFn.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
 
 
-class _LnReluResFn(torch.autograd.Function):
-    """relu(LayerNorm(y)) + res in one pass (models.py:641-655)."""
-
-    @staticmethod
-    def forward(ctx, y, gamma, beta, res, eps):
-        K = kernels.default()
-        M, W = y.shape
-        z = torch.empty((M, W), dtype=torch.float32, device=y.device)
-        stats = torch.empty((M, 2), dtype=torch.float32, device=y.device)
-        K.ln_relu_res_fwd(y, gamma, beta, eps, res, z, stats)
-        ctx.save_for_backward(y, stats, gamma, beta)
-        ctx.has_res = res is not None
-        ctx.params = (gamma, beta)
-        return z
-
-    @staticmethod
-    def backward(ctx, dz):
-        K = kernels.default()
-        y, stats, gamma, beta = ctx.saved_tensors
-        dz = dz.contiguous()
-        dy = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-        dgamma, dbeta = _ln_bwd(K, *ctx.params, dz, y, stats, gamma, beta, dy)
-        return dy, dgamma, dbeta, (dz if ctx.has_res else None), None
-
-
-def _ln_bwd(K, pg, pb, dz, y, stats, gamma, beta, dy, **dres):
-    """The LayerNorm backward's row pass (dy, and ``dres=``) with its dgamma / dbeta sums, which go:
-    without both sinks into new tensors (returned); with them and nothing overlapping straight into
-    the sinks; while overlapping into a workspace as partials, and adding those to the sinks is
-    queued side work (it has no grouped form).  Returns (dgamma, dbeta) for autograd."""
-    sg, sb = _sink(pg), _sink(pb)
-    if sg is None or sb is None:
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, dgamma, dbeta, **dres)
-        return dgamma, dbeta
-    if not paramgrads.overlapping():
-        K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, sg, sb, accumulate=True, **dres)
-    else:
-        W = y.shape[1]
-        ws = K.ln_workspace(W, y.device)
-        K.ln_relu_res_bwd(dz, y, stats, gamma, beta, dy, None, None, ws=ws, **dres)
-        param_launch(lambda: K.ln_relu_res_bwd_params(W, sg, sb, ws, accumulate=True), ws)
-    return None, None
-
-
-def ln_relu_res(y, norm, res=None):
-    """F.relu(norm(y)) + res for a torch.nn.LayerNorm ``norm`` (elementwise affine)."""
-    _dev_check(y)
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    if res is not None and res.stride(1) != 1:
-        res = res.contiguous()
-    return _LnReluResFn.apply(y, norm.weight, norm.bias, res, norm.eps)
-
-
-# ---- LayerNorm tails of the other zoo models (ln_act.hip): LayerNorm -> act (+ res) (-> LayerNorm) ----
+# ---- the LayerNorm row pass (ln_act.hip), the flagship's and the other zoo models': LayerNorm -> act (+ res)
+# (-> LayerNorm) ----
 LN_WIDTHS = (32, 64, 128, 256, 512)
 
 
@@ -523,10 +472,10 @@ def _rows_f32(t, W, what):
 
 
 def _ln_act_bwd(K, cfg, params, dz, y, stats, res, stats2, dy, dres=None):
-    """The row pass of the backward and its parameter sums, which go where ``_ln_bwd``'s go: without every
-    sink into new tensors (returned); with them and nothing overlapping straight into the sinks; while
-    overlapping into a workspace as partials, and adding those to the sinks is queued side work.  Returns
-    (dgamma, dbeta, dgamma2, dbeta2) for autograd."""
+    """The row pass of the backward (dy, and ``dres=``) with its parameter sums, which go: without every sink
+    into new tensors (returned); with them and nothing overlapping straight into the sinks; while overlapping
+    into a workspace as partials, and adding those to the sinks is queued side work (it has no grouped form).
+    Returns (dgamma, dbeta, dgamma2, dbeta2) for autograd."""
     code, slope = cfg
     gamma, beta, gamma2, beta2 = params
     n2 = gamma2 is not None
@@ -569,15 +518,21 @@ class _LnActResFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz):
-        K = kernels.default()
-        y, stats, res, stats2 = ctx.saved_tensors
-        n2 = ctx.params[2] is not None
-        dz = dz.contiguous()
-        dy = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-        # without the second norm d(res) is dz itself; with it the kernel writes du
-        dres = torch.empty_like(dy) if (ctx.has_res and n2) else None
-        dg, db, dg2, db2 = _ln_act_bwd(K, ctx.cfg, ctx.params, dz, y, stats, res, stats2, dy, dres)
-        return dy, ((dres if n2 else dz) if ctx.has_res else None), dg, db, dg2, db2, None, None, None, None
+        dy, dres, dg, db, dg2, db2 = _ln_act_res_backward(ctx.cfg, ctx.params, ctx.has_res, *ctx.saved_tensors, dz)
+        return dy, dres, dg, db, dg2, db2, None, None, None, None
+
+
+def _ln_act_res_backward(cfg, params, has_res, y, stats, res, stats2, dz):
+    """``_LnActResFn``'s backward on its operands (``res``: the forward's, read with the second norm only):
+    (dy, dres, dgamma, dbeta, dgamma2, dbeta2)."""
+    K = kernels.default()
+    n2 = params[2] is not None
+    dz = dz.contiguous()
+    dy = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+    # without the second norm d(res) is dz itself; with it the kernel writes du
+    dres = torch.empty_like(dy) if (has_res and n2) else None
+    dg, db, dg2, db2 = _ln_act_bwd(K, cfg, params, dz, y, stats, res, stats2, dy, dres)
+    return dy, ((dres if n2 else dz) if has_res else None), dg, db, dg2, db2
 
 
 def ln_act_res(y, norm, act, res=None, norm2=None):
@@ -750,46 +705,6 @@ def _joined(a, b):
     return torch.cat([a, b])
 
 
-class _DualLnReluResFn(torch.autograd.Function):
-    """relu(norm(lin1(x))) + lin2(x) -- the residual blocks of models.py:638-649 -- as
-    ONE GEMM Y = x [W1; W2]^T + [b1; b2] and one row pass over Y = [y | res].  The backward's LN
-    pass writes dY = [dy | dz] packed, so dx is ONE GEMM (K = 2W) and, with the pairs adjacent in
-    FlatAdam's buffer (``flat_parameters``), dW and db are one GEMM / one column sum each."""
-
-    @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, eps):
-        K = kernels.default()
-        x = x.contiguous()
-        M = x.shape[0]
-        w = W1.shape[0]
-        Wc = _joined(W1, W2)
-        bc = _joined(b1, b2)
-        Y = torch.empty((M, 2 * w), dtype=torch.float32, device=x.device)
-        K.gemm(0, 0, M, 2 * w, x.shape[1], x, Wc.contiguous(), Y, bias=bc.contiguous(), name="gemm_fwd")
-        z = torch.empty((M, w), dtype=torch.float32, device=x.device)
-        stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
-        K.ln_relu_res_fwd(Y[:, :w], gamma, beta, eps, Y[:, w:], z, stats)
-        ctx.save_for_backward(x, Y, stats, gamma, beta)
-        ctx.params = (W1, b1, W2, b2, gamma, beta)
-        return z
-
-    @staticmethod
-    def backward(ctx, dz):
-        K = kernels.default()
-        x, Y, stats, gamma, beta = ctx.saved_tensors
-        W1, b1, W2, b2, pg, pb = ctx.params
-        dz = dz.contiguous()
-        M, w = dz.shape
-        dY = torch.empty((M, 2 * w), dtype=torch.float32, device=dz.device)
-        dgamma, dbeta = _ln_bwd(K, pg, pb, dz, Y[:, :w], stats, gamma, beta, dY[:, :w], dres=dY[:, w:])
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = K.gemm(0, 1, M, x.shape[1], 2 * w, dY, _joined(W1, W2).contiguous(), torch.empty_like(x),
-                        name="gemm_dx")
-        dW1, db1, dW2, db2 = _dual_param_grads(K, W1, b1, W2, b2, dY, x)
-        return dx, dW1, db1, dW2, db2, dgamma, dbeta, None
-
-
 def _dual_param_grads(K, W1, b1, W2, b2, dY, x):
     """dW / db of a dual-Linear pair from its packed output gradient dY = [dy1 | dy2] and input x:
     into the parameters' sinks (queued side work; returns Nones) or new tensors (returned)."""
@@ -836,18 +751,11 @@ def _ln_param_grads(K, gamma, beta, ws, rows):
     return out[:W], out[W:]
 
 
-def dual_ln_relu_res(x, lin1, lin2, norm):
-    """relu(norm(lin1(x))) + lin2(x) (models.py:638-641 / :646-649) on the fused kernels."""
-    _dev_check(x)
-    return _DualLnReluResFn.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, norm.weight, norm.bias,
-                                  norm.eps)
-
-
 class _DualLnActResFn(torch.autograd.Function):
-    """norm2(act(norm(lin1(x))) + lin2(x)) -- the residual blocks of models.py:437-526, :528-612 and
-    :693-773 -- as ``_DualLnReluResFn`` does it: ONE GEMM Y = x [W1; W2]^T + [b1; b2], one row pass over
-    Y = [y | res] (ln_act.hip), a packed dY = [dy | dres] from the backward's row pass, so dx is ONE GEMM
-    and, with the pairs adjacent in FlatAdam's buffer, dW and db one GEMM."""
+    """norm2(act(norm(lin1(x))) + lin2(x)) -- the residual blocks of models.py:638-649 (relu, no norm2),
+    :437-526, :528-612 and :693-773 -- as ONE GEMM Y = x [W1; W2]^T + [b1; b2] and one row pass over
+    Y = [y | res] (ln_act.hip).  The backward's row pass writes dY = [dy | dres] packed, so dx is ONE GEMM
+    (K = 2W) and, with the pairs adjacent in FlatAdam's buffer (``flat_parameters``), dW and db one GEMM."""
 
     @staticmethod
     def forward(ctx, x, W1, b1, W2, b2, gamma, beta, gamma2, beta2, eps, eps2, code, slope):
@@ -870,20 +778,22 @@ class _DualLnActResFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz):
-        K = kernels.default()
-        x, Y, stats, stats2 = ctx.saved_tensors
-        W1, b1, W2, b2 = ctx.params[:4]
-        dz = dz.contiguous()
-        M, w = dz.shape
-        dY = torch.empty((M, 2 * w), dtype=torch.float32, device=dz.device)
-        dg, db, dg2, db2 = _ln_act_bwd(K, ctx.cfg, ctx.params[4:], dz, Y[:, :w], stats, Y[:, w:], stats2, dY[:, :w],
-                                       dres=dY[:, w:])
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = K.gemm(0, 1, M, x.shape[1], 2 * w, dY, _joined(W1, W2).contiguous(), torch.empty_like(x),
-                        name="gemm_dx")
-        dW1, db1, dW2, db2_ = _dual_param_grads(K, W1, b1, W2, b2, dY, x)
-        return dx, dW1, db1, dW2, db2_, dg, db, dg2, db2, None, None, None, None
+        return _dual_ln_act_res_backward(ctx.cfg, ctx.params, ctx.needs_input_grad[0], *ctx.saved_tensors, dz) \
+            + (None,) * 4
+
+
+def _dual_ln_act_res_backward(cfg, params, need_dx, x, Y, stats, stats2, dz):
+    """``_DualLnActResFn``'s backward on its operands: (dx, dW1, db1, dW2, db2, dgamma, dbeta, dgamma2, dbeta2)."""
+    K = kernels.default()
+    W1, b1, W2, b2 = params[:4]
+    dz = dz.contiguous()
+    M, w = dz.shape
+    dY = torch.empty((M, 2 * w), dtype=torch.float32, device=dz.device)
+    dg, db, dg2, db2 = _ln_act_bwd(K, cfg, params[4:], dz, Y[:, :w], stats, Y[:, w:], stats2, dY[:, :w], dres=dY[:, w:])
+    dx = None
+    if need_dx:
+        dx = K.gemm(0, 1, M, x.shape[1], 2 * w, dY, _joined(W1, W2).contiguous(), torch.empty_like(x), name="gemm_dx")
+    return (dx,) + _dual_param_grads(K, W1, b1, W2, b2, dY, x) + (dg, db, dg2, db2)
 
 
 def dual_ln_act_res(x, lin1, lin2, norm, act, norm2=None):
@@ -967,7 +877,6 @@ class _FusedTailFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dcoords):
-        import types
         x, Y1, st1, z1, Y2, st2, z2, y3, st3, z3 = ctx.saved_tensors
         Wa, ba, Wal, bal, ga, bea, W1, b1, W1al, b1al, g1, be1, W2, b2, g2, be2, W3, b3 = ctx.params
         if FUSED_TAIL_BWD:
@@ -998,20 +907,14 @@ class _FusedTailFn(torch.autograd.Function):
             dWa, dba, dWal, dbal = _dual_param_grads(K, Wa, ba, Wal, bal, dY1, x)
             return (dx if ctx.needs_input_grad[0] else None, dWa, dba, dWal, dbal, dga, dbea, dW1, db1, dW1al, db1al,
                     dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3, None, None, None, None)
-        T = (True,) * 8
-
-        def c(**kw):
-            return types.SimpleNamespace(needs_input_grad=T, **kw)
-
-        dz3, dW3, db3 = _LinearFn.backward(c(saved_tensors=(z3, W3), params=(W3, b3), has_bias=True), dcoords)
-        dy3, dg2, dbe2, _, _ = _LnReluResFn.backward(c(saved_tensors=(y3, st3, g2, be2), params=(g2, be2),
-                                                       has_res=False), dz3)
-        dz2, dW2, db2 = _LinearFn.backward(c(saved_tensors=(z2, W2), params=(W2, b2), has_bias=True), dy3)
-        dz1, dW1, db1, dW1al, db1al, dg1, dbe1, _ = _DualLnReluResFn.backward(
-            c(saved_tensors=(z1, Y2, st2, g1, be1), params=(W1, b1, W1al, b1al, g1, be1)), dz2)
-        ctx1 = types.SimpleNamespace(needs_input_grad=(ctx.needs_input_grad[0],) + T[1:],
-                                     saved_tensors=(x, Y1, st1, ga, bea), params=(Wa, ba, Wal, bal, ga, bea))
-        dx, dWa, dba, dWal, dbal, dga, dbea, _ = _DualLnReluResFn.backward(ctx1, dz1)
+        relu = (kernels.HipKernels.ACT_RELU, 0.0)
+        dz3, dW3, db3 = _linear_backward(W3, b3, z3, dcoords)
+        dy3, _, dg2, dbe2, _, _ = _ln_act_res_backward(relu, (g2, be2, None, None), False, y3, st3, None, None, dz3)
+        dz2, dW2, db2 = _linear_backward(W2, b2, z2, dy3)
+        dz1, dW1, db1, dW1al, db1al, dg1, dbe1, _, _ = _dual_ln_act_res_backward(
+            relu, (W1, b1, W1al, b1al, g1, be1, None, None), True, z1, Y2, st2, None, dz2)
+        dx, dWa, dba, dWal, dbal, dga, dbea, _, _ = _dual_ln_act_res_backward(
+            relu, (Wa, ba, Wal, bal, ga, bea, None, None), ctx.needs_input_grad[0], x, Y1, st1, None, dz1)
         return (dx, dWa, dba, dWal, dbal, dga, dbea, dW1, db1, dW1al, db1al, dg1, dbe1, dW2, db2, dg2, dbe2,
                 dW3, db3, None, None, None, None)
 

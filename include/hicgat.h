@@ -453,42 +453,23 @@ int hicgat_colsum(const float *A, int64_t lda, int K, int N, float *out, int acc
                   size_t workspace_bytes, hicgat_stream_t stream);
 size_t hicgat_colsum_workspace_bytes(int K, int N);
 
-/* ---- a6: LayerNorm + ReLU (+ residual) of the flagship tail (models.py:641-655) --------------
- * z = relu(LayerNorm(y) * gamma + beta) + res (res may be NULL), W in {64, 128, 256}, eps as in
- * torch.nn.LayerNorm (biased variance); row_stats [M, 2] = (mean, rstd) saved for the backward.
- * Backward: dy (ld lddy), dgamma/dbeta (accumulate != 0 adds into them); dres = dz: the caller's
- * dz, or (dres != NULL) also written to dres (ld lddres), e.g. beside dy in one packed [dy | dres]
- * row for the fused dual-Linear backward.  workspace: hicgat_ln_relu_res_workspace_bytes(W). */
-int hicgat_ln_relu_res_fwd(const float *y, int64_t ldy, int M, int W, const float *gamma, const float *beta,
-                           float eps, const float *res, int64_t ldr, float *z, float *row_stats,
-                           hicgat_stream_t stream);
-int hicgat_ln_relu_res_bwd(const float *dz, const float *y, int64_t ldy, int M, int W, const float *row_stats,
-                           const float *gamma, const float *beta, float *dy, int64_t lddy, float *dres,
-                           int64_t lddres, float *dgamma, float *dbeta, int accumulate, void *workspace,
-                           size_t workspace_bytes, hicgat_stream_t stream);
-size_t hicgat_ln_relu_res_workspace_bytes(int W);
-/* dgamma = dbeta = NULL in hicgat_ln_relu_res_bwd: only dy (and dres) are written and the per-wave
- * partials stay in the workspace; this call then reduces them into dgamma / dbeta (fixed order, the
- * same bits as the one-call form) -- on another stream after an event, so the parameter
- * reduction leaves the backward's critical path. */
-int hicgat_ln_relu_res_bwd_params(int W, float *dgamma, float *dbeta, int accumulate, void *workspace,
-                                  size_t workspace_bytes, hicgat_stream_t stream);
-
-/* ---- LayerNorm tails of the other zoo models (ln_act.hip; models.py:321-377, :379-435, :437-526,
- * :528-612, :693-773, :776-832): LayerNorm -> activation (+ residual) (-> a second LayerNorm) as one
- * row pass:
+/* ---- a6 and the zoo's other LayerNorm tails (ln_act.hip; the flagship's models.py:641-655, and :321-377,
+ * :379-435, :437-526, :528-612, :693-773, :776-832): LayerNorm -> activation (+ residual) (-> a second
+ * LayerNorm) as one row pass:
  *   u = act(LayerNorm(y; gamma, beta, eps)) + res            (res may be NULL)
  *   z = LayerNorm(u; gamma2, beta2, eps2)                    (gamma2 != NULL; else z = u)
  * torch.nn.LayerNorm semantics (biased variance about the mean, eps inside the square root).  act is a
  * HICGAT_ACT_* code: none, relu, leaky_relu (x > 0 ? x : x * slope) or gelu = 0.5 x (1 + erf(x / sqrt 2))
  * (F.gelu's default, not the tanh form).  W in {32, 64, 128, 256, 512}.  y / res / z rows are ldy / ldr /
  * ldz floats apart (column slices of one [M, 2W] buffer pass ld = 2W).  row_stats [M, 2] = (mean, rstd)
- * and, with the second norm, row_stats2 [M, 2] = (mean2, rstd2) are saved for the backward.  With relu and
- * no second norm the results are hicgat_ln_relu_res_fwd / _bwd's, bit for bit.
+ * and, with the second norm, row_stats2 [M, 2] = (mean2, rstd2) are saved for the backward.  The
+ * flagship's blocks are relu without a second norm at W = 256, 128 (res given) and 64 (res NULL).
  * Backward (recomputes pre = yhat gamma + beta, and u from y and res with the second norm: pass the
  * forward's res, gamma2 and row_stats2 then; res is not read otherwise):
  *   du = rstd2 (dz gamma2 - mean(.) - uhat mean(. uhat)), or dz without the second norm;
- *   dres = du, written to dres (ld lddres) when dres != NULL, e.g. beside dy in a packed [dy | dres] row;
+ *   dres = du, written to dres (ld lddres) when dres != NULL (without the second norm a NULL dres loses
+ *   nothing: d(res) is the caller's dz) -- e.g. beside dy, dy = dY, dres = dY + W, lddy = lddres = 2W, so that
+ *   one packed [dy | dres] row feeds the dual-Linear backward's single dx and dW GEMMs;
  *   g = du act'(pre): relu [pre > 0], leaky_relu (pre > 0 ? 1 : slope), gelu Phi(pre) + pre phi(pre);
  *   dy (ld lddy) = rstd (g gamma - mean(.) - yhat mean(. yhat));
  *   dgamma = sum g yhat, dbeta = sum g, dgamma2 = sum dz uhat, dbeta2 = sum dz over the rows: per-wave
@@ -522,7 +503,7 @@ int hicgat_act_bwd(const float *dy, const float *x, int M, int W, int act, float
                    hicgat_stream_t stream);
 
 /* ---- The flagship's MLP tail forward in one launch (tail_fused.hip; replaces the dual-Linear GEMMs,
- * ln_relu_res passes and Linear GEMMs of models.py:637-659 for GATNetSelectiveResidualsUpdated) ----
+ * LayerNorm row passes and Linear GEMMs of models.py:637-659 for GATNetSelectiveResidualsUpdated) ----
  * x [M][512] (ld ldx, 16-B aligned rows): the GATConv output after its relu.  W1c [512][512] = [W_densea;
  * W_align_densea], b1c [512]; g1/be1 [256] = norm_a; W2c [256][256] = [W_dense1; W_align_dense1], b2c
  * [256]; g2/be2 [128] = norm1; W3 [64][128] / b3 = dense2; g3/be3 [64] = norm2; W4 [3][64] / b4 = dense3.

@@ -414,7 +414,7 @@ def test_ln_relu_res_and_dual_linear_match_torch(w, with_res):
         norm.bias.uniform_(-0.2, 0.2)
     x = torch.randn(5003, 2 * w, device=DEV, requires_grad=True)
     y, r = hicgat.ops.dual_linear(x, lin1, lin2)
-    z = hicgat.ops.ln_relu_res(y, norm, r if with_res else None)
+    z = hicgat.ops.ln_act_res(y, norm, "relu", res=r if with_res else None)
     g = torch.randn_like(z)
     (z * g).sum().backward()
     mine = [t.grad.clone() for t in (x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, norm.weight, norm.bias)]

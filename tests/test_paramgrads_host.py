@@ -115,8 +115,8 @@ class Rig:
         self.log("colsum", A, out, f"acc={accumulate}")
         return out
 
-    def ln_relu_res_bwd_params(self, W, dgamma, dbeta, ws, accumulate=False):
-        self.log("ln_relu_res_bwd_params", W, dgamma, dbeta, ws, f"acc={accumulate}")
+    def ln_act_res_bwd_params(self, W, dgamma, dbeta, ws, accumulate=False):
+        self.log("ln_act_res_bwd_params", W, dgamma, dbeta, ws, f"acc={accumulate}")
 
     def param_grads_grouped(self, wjobs, cjobs, target_wgs=None, small_m=None):
         # a column-sum job always as (src, dst, accumulate, weights)
@@ -131,7 +131,7 @@ class Rig:
         ops._wb_grad_to(self, m.dense3.weight, m.dense3.bias, t.dc, t.z3)
         if ln2_per_layer:
             sg, sb, ws = m.norm2.weight.grad, m.norm2.bias.grad, t.ws3
-            pg.param_launch(lambda: self.ln_relu_res_bwd_params(64, sg, sb, ws, accumulate=True), ws)
+            pg.param_launch(lambda: self.ln_act_res_bwd_params(64, sg, sb, ws, accumulate=True), ws)
         else:
             ops._ln_param_grads(self, m.norm2.weight, m.norm2.bias, t.ws3, ROWS)
         ops._wb_grad_to(self, m.dense2.weight, m.dense2.bias, t.dy3, t.z2)
@@ -275,7 +275,7 @@ def test_an_item_without_a_job_makes_the_whole_flush_per_item(rig):
     with pg.overlapped_param_grads():
         assert rig.backward(ln2_per_layer=True)[0] == 0
     want = per_item("side0")
-    want[1] = ("ln_relu_res_bwd_params", "side0", "64 d_norm2.weight[64] d_norm2.bias[64] ws3[384] acc=True")
+    want[1] = ("ln_act_res_bwd_params", "side0", "64 d_norm2.weight[64] d_norm2.bias[64] ws3[384] acc=True")
     assert rig.trace == [("record", "main", "e1"), ("source_pass", "main", ""), ("wait", "side0", "e1"), *want,
                          ("join", "main", "side0")]
 
@@ -338,7 +338,7 @@ def test_side_lane_forks_a_named_lane_and_keeps_until_the_join(rig):
 def test_grouped_param_grads_collects_jobs_and_launches_the_rest(rig):
     with pg.grouped_param_grads():
         rig.tail(ln2_per_layer=True)
-        assert rig.trace == [("ln_relu_res_bwd_params", "main",
+        assert rig.trace == [("ln_act_res_bwd_params", "main",
                               "64 d_norm2.weight[64] d_norm2.bias[64] ws3[384] acc=True")]
     keep = pg.grouped_flush(rig, [rig.lin_l()], target_wgs=256, small_m=16)
     assert len(keep) == 10 and keep[0] is rig.t.dc

@@ -103,7 +103,7 @@ def main():
                                                        out2, rs),
         "gat_agg_bwd_src_tiled": lambda K: K.agg_bwd_src_tiled(tiles(), h, a_s, a_d, rs, dout, al, ar, 0.2, dh, da),
         "colsum_20000x512": lambda K: K.colsum(out, cs),
-        "ln_bwd_256": lambda K: K.ln_relu_res_bwd(ya, ya, lns, g256, g256, ya2, g256b, g256c),
+        "ln_bwd_256": lambda K: K.ln_act_res_bwd(ya, ya, lns, g256, g256, K.ACT_RELU, 0.0, ya2, g256b, g256c),
         "adam": lambda K: K.adam(flat, g, m, v, flat.numel(), 1e-3, 0.9, 0.999, 1e-8, 1),
         "gemm_dw_512x512": lambda K: hicgat.ops.weight_grad(K, dh, x),
         "gemm_fwd_densea": lambda K: K.gemm(0, 0, n, 256, 512, out, Wa, ya, bias=ba),
