@@ -3,6 +3,7 @@
 //   agg_bwd_rows_row  destination side of the backward without a gather
 //   agg_bwd_dst_row   destination side, stand-alone gathering form
 //   agg_bwd_src_row   source side
+//   attn_mask_row     the attention-dropout keep bits of a row's edges (tests, tools)
 // The __global__ kernels around them only pick the row: the (2, 256) entry kernels with their
 // measured launch parameters in gat_fwd.hip / gat_bwd.hip, every other shape's in gat_generic.hip.
 // Supported set:  C % 128 == 0,  D = H*C a multiple of 256,  D <= 1024,  H <= 4.
@@ -25,6 +26,7 @@
 // over a half wave (formed here as whole-wave sums of values that the other half contributes 0 to).
 #pragma once
 #include "common.hpp"
+#include "philox.hpp"
 
 namespace hicgat {
 
@@ -95,12 +97,19 @@ __device__ __forceinline__ float4 f4_sub(float4 a, float4 b) {
 // (rowptr/col), but only the edges of the sparse remainder (rowptr_s/col_s) are gathered, and the
 // raw sums (no bias, no activation) go to out/out2 with S3 of those edges; the matrix-core pass over
 // the row's dense 32x32 tiles adds the rest and applies the epilogue.
-template <int H, int C, bool TRAIN, int ACT, bool SPLIT>
+//
+// DROP (attention dropout, PyG's F.dropout(alpha, p) in message()): each alpha_ij is multiplied by
+// m_ij in {0, 1/(1-p)} (philox.hpp attn_factor: one Philox call per edge, where the lane that owns the
+// edge forms its weights -- once per 64-edge chunk, never inside the gather loop).  out and out2 take
+// the masked weights, S3 the unmasked one; the softmax statistics are those of the undropped row.
+// No SPLIT form.  With DROP = false `mk` is unused and the body is what it was without it.
+template <int H, int C, bool TRAIN, int ACT, bool SPLIT, bool DROP = false>
 __device__ __forceinline__ void agg_fwd_row(
     int i, const int *__restrict__ rowptr, const int *__restrict__ col, const int *__restrict__ rowptr_s,
     const int *__restrict__ col_s, const float *__restrict__ h, const float *__restrict__ a_src,
     const float *__restrict__ a_dst, const float *__restrict__ bias, float ns, float *__restrict__ out,
-    float *__restrict__ out2, float *__restrict__ row_stats) {
+    float *__restrict__ out2, float *__restrict__ row_stats, const AttnMaskArgs &mk = AttnMaskArgs{}) {
+  static_assert(!(DROP && SPLIT), "the tiled form has no attention dropout");
   using S = Shape<H, C>;
   constexpr int U = S::UFwd, V = S::V, Q = S::Q;
   const int lane = lane_id();
@@ -142,6 +151,7 @@ __device__ __forceinline__ void agg_fwd_row(
   for (int hh = 0; hh < H; ++hh) t[hh] = 0.f;
   const int gbeg = SPLIT ? rowptr_s[i] : beg, gend = SPLIT ? rowptr_s[i + 1] : end;
   const int *__restrict__ gcol = SPLIT ? col_s : col;
+  const uint32_t step = DROP ? mask_step(mk) : 0u;
   for (int base = gbeg; base < gend; base += 64) {
     const int e = base + lane;
     int j = i;  // padded slots gather the (valid) own row with weight 0
@@ -158,6 +168,15 @@ __device__ __forceinline__ void agg_fwd_row(
         if (TRAIN) {
           q[hh] = p[hh] * (ee > 0.f ? 1.f : ns);
           t[hh] += q[hh];
+        }
+      }
+      if (DROP) {
+        float f[H];
+        attn_factor<H>(mk, step, i, j, f);
+#pragma unroll
+        for (int hh = 0; hh < H; ++hh) {
+          p[hh] *= f[hh];
+          q[hh] *= f[hh];
         }
       }
     }
@@ -377,12 +396,17 @@ __device__ __forceinline__ void agg_bwd_dst_row(int i, const int *__restrict__ r
 // SPLIT (the tiled form, gat_tiles.hip): rowptr/col are the sparse remainder of the row's edges;
 // dh gets the raw sum (no logit terms) and da_src the remainder's share of da_src; the matrix-core
 // pass over the dense tiles adds the rest and finishes both.
-template <int H, int C, bool SPLIT>
+// DROP: the two accumulated vectors take the masked weights alpha_ir m_ir, the scalar sum the unmasked
+// one (delta_i already carries the mask); m_ir is the forward's bit of edge (i -> r), recomputed from
+// (col[e], r).  No SPLIT form.
+template <int H, int C, bool SPLIT, bool DROP = false>
 __device__ __forceinline__ void agg_bwd_src_row(
     int r, const int *__restrict__ rowptr, const int *__restrict__ col, const float *__restrict__ h,
     const float *__restrict__ a_src, const float *__restrict__ a_dst, const float *__restrict__ row_stats,
     int64_t ldr, const float *__restrict__ dout, int64_t ldq, const float *__restrict__ att_s,
-    const float *__restrict__ att_d, float ns, float *__restrict__ dh, float *__restrict__ da_src) {
+    const float *__restrict__ att_d, float ns, float *__restrict__ dh, float *__restrict__ da_src,
+    const AttnMaskArgs &mk = AttnMaskArgs{}) {
+  static_assert(!(DROP && SPLIT), "the tiled form has no attention dropout");
   using S = Shape<H, C>;
   constexpr int U = S::USrc, V = S::V, Q = S::Q, TR = S::TR, HP = S::HP;
   const int lane = lane_id();
@@ -400,6 +424,7 @@ __device__ __forceinline__ void agg_bwd_src_row(
   float4 acc[V], c[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) acc[v] = c[v] = z4;
+  const uint32_t step = DROP ? mask_step(mk) : 0u;
   for (int base = beg; base < end; base += 64) {
     const int e = base + lane;
     int inb = r;
@@ -416,6 +441,15 @@ __device__ __forceinline__ void agg_bwd_src_row(
         al[hh] = expf(lrelu(ee, ns) - rs[hh]) / (rs[H + hh] + 1e-16f);
         A[hh] = al[hh] * (ee > 0.f ? 1.f : ns);
         sb[hh] = fmaf(A[hh], rs[2 * H + hh], sb[hh]);
+      }
+      if (DROP) {
+        float f[H];
+        attn_factor<H>(mk, step, inb, r, f);
+#pragma unroll
+        for (int hh = 0; hh < H; ++hh) {
+          al[hh] *= f[hh];
+          A[hh] *= f[hh];
+        }
       }
     }
     const int cnt = min(64, end - base);
@@ -470,6 +504,21 @@ __device__ __forceinline__ void agg_bwd_src_row(
   if (lane == 0) {
 #pragma unroll
     for (int hh = 0; hh < H; ++hh) da_src[(size_t)r * H + hh] = ds[hh];
+  }
+}
+
+// ---- the keep bits of row i's edges, [nnz, H] uint8 in self-looped CSR order, from the device
+// function the DROP passes use (philox.hpp attn_keep).
+template <int H>
+__device__ __forceinline__ void attn_mask_row(int i, const int *__restrict__ rowptr, const int *__restrict__ col,
+                                              const AttnMaskArgs &mk, uint8_t *__restrict__ mask) {
+  const uint32_t step = mask_step(mk);
+  const int beg = rowptr[i], end = rowptr[i + 1];
+  for (int e = beg + lane_id(); e < end; e += 64) {
+    bool keep[H];
+    attn_keep<H>(mk, step, i, col[e], keep);
+#pragma unroll
+    for (int hh = 0; hh < H; ++hh) mask[(size_t)e * H + hh] = keep[hh] ? 1 : 0;
   }
 }
 

@@ -55,6 +55,21 @@ __global__ __launch_bounds__(256) void agg_bwd_src_h2c256_kernel(
                                    da_src);
 }
 
+// The source pass with attention dropout (DROP; gat_agg.hpp): a kernel of its own, so that the one
+// above keeps its arguments and code.  No SPLIT form, and no occupancy cap: nobody has measured one.
+template <bool REMAP>
+__global__ __launch_bounds__(256) void agg_bwd_src_drop_h2c256_kernel(
+    const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
+    const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
+    const float *__restrict__ row_stats, int64_t ldr, const float *__restrict__ dout, int64_t ldq,
+    const float *__restrict__ att_s, const float *__restrict__ att_d, float ns,
+    float *__restrict__ dh, float *__restrict__ da_src, AttnMaskArgs mk) {
+  const int r = row_begin + (REMAP ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x) * 4 + wave_in_block();
+  if (r < row_end)
+    agg_bwd_src_row<2, 256, false, true>(r, rowptr, col, h, a_src, a_dst, row_stats, ldr, dout, ldq, att_s, att_d, ns,
+                                         dh, da_src, mk);
+}
+
 template <int ACT>
 __global__ __launch_bounds__(256) void agg_bwd_rows_kernel(int row_begin, int row_end,
                                                            const float *__restrict__ g,
@@ -183,6 +198,11 @@ int agg_bwd_src_generic_launch(const int *rowptr, const int *col, int H, int C, 
                                const float *h, const float *a_src, const float *a_dst, const float *row_stats,
                                int64_t ldr, const float *dout, int64_t ldq4, const float *att_s, const float *att_d,
                                float ns, float *dh, float *da_src, bool remap, hipStream_t s);
+int agg_bwd_src_drop_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
+                                    const float *h, const float *a_src, const float *a_dst, const float *row_stats,
+                                    int64_t ldr, const float *dout, int64_t ldq4, const float *att_s,
+                                    const float *att_d, float ns, float *dh, float *da_src, bool remap,
+                                    const AttnMaskArgs &mk, hipStream_t s);
 
 }  // namespace hicgat
 
@@ -238,6 +258,42 @@ extern "C" int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col,
     hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<false, false>), grid, block, 0, (hipStream_t)stream, rowptr, col,
                        row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout, ld_dout / 4, att_src,
                        att_dst, neg_slope, dh, da_src);
+  HICGAT_CHECK_LAUNCH();
+  return HICGAT_OK;
+}
+
+// ---- attention dropout: hicgat_gat_agg_bwd_src with the forward's keep factors recomputed ---------
+extern "C" int hicgat_gat_agg_drop_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H, int C,
+                                           int row_begin, int row_end, const float *h, const float *a_src,
+                                           const float *a_dst, const float *row_stats, int64_t ld_stats,
+                                           const float *dout, int64_t ld_dout, const float *att_src,
+                                           const float *att_dst, float neg_slope, float *dh, float *da_src,
+                                           int flags, double p, uint64_t seed, const int64_t *step_counter,
+                                           int64_t step_value, uint32_t site, hicgat_stream_t stream) {
+  if (flags & ~HICGAT_SRC_ROUND_ROBIN) return HICGAT_EINVAL;
+  const bool remap = !(flags & HICGAT_SRC_ROUND_ROBIN);
+  if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
+  if (!p_ok(p) || !attn_site_ok(site) || misaligned(step_counter, 8)) return HICGAT_EINVAL;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
+  if (ld_stats < 4 * H || ld_stats % 4 || ld_dout < H * C || ld_dout % 4) return HICGAT_EINVAL;
+  if (row_end == row_begin) return HICGAT_OK;
+  if (!rowptr || !col || !h || !a_src || !a_dst || !row_stats || !dout || !att_src || !att_dst ||
+      !dh || !da_src)
+    return HICGAT_EINVAL;
+  const AttnMaskArgs mk = attn_mask_args(p, seed, step_counter, step_value, site);
+  hipStream_t s = (hipStream_t)stream;
+  if (H != 2 || C != 256)
+    return agg_bwd_src_drop_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats,
+                                           dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, remap, mk, s);
+  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+  if (remap)
+    hipLaunchKernelGGL((agg_bwd_src_drop_h2c256_kernel<true>), grid, block, 0, s, rowptr, col, row_begin, row_end, h,
+                       a_src, a_dst, row_stats, ld_stats, dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src,
+                       mk);
+  else
+    hipLaunchKernelGGL((agg_bwd_src_drop_h2c256_kernel<false>), grid, block, 0, s, rowptr, col, row_begin, row_end, h,
+                       a_src, a_dst, row_stats, ld_stats, dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src,
+                       mk);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
 }

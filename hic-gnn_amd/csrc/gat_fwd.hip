@@ -70,7 +70,27 @@ int agg_fwd_split_launch(const int *rowptr, const int *col, const int *rowptr_s,
   return HICGAT_OK;
 }
 
+// The same row body with attention dropout (DROP; gat_agg.hpp): a kernel of its own, so that the one
+// above keeps its arguments and code.  No SPLIT form, and no occupancy cap: nobody has measured one.
+template <bool TRAIN, int ACT>
+__global__ __launch_bounds__(256, 1) void agg_fwd_drop_h2c256_kernel(
+    const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
+    const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
+    const float *__restrict__ bias, float ns, float *__restrict__ out, float *__restrict__ out2,
+    float *__restrict__ row_stats, AttnMaskArgs mk) {
+  const int i = row_begin + xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_in_block();
+  if (i < row_end)
+    agg_fwd_row<2, 256, TRAIN, ACT, false, true>(i, rowptr, col, nullptr, nullptr, h, a_src, a_dst, bias, ns, out,
+                                                 out2, row_stats, mk);
+}
+
 // gat_generic.hip: the supported-shape rule and the kernels of every supported shape but (2, 256)
+int agg_fwd_drop_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
+                                const float *h, const float *a_src, const float *a_dst, const float *bias, float ns,
+                                int act, float *out, float *out2, float *row_stats, const AttnMaskArgs &mk,
+                                hipStream_t s);
+int attn_mask_launch(const int *rowptr, const int *col, int N, int H, const AttnMaskArgs &mk, uint8_t *mask,
+                     hipStream_t s);
 bool gat_shape_supported(int H, int C);
 int agg_fwd_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
                            const float *h, const float *a_src, const float *a_dst, const float *bias, float ns,
@@ -127,4 +147,49 @@ extern "C" int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int
 #undef HICGAT_FWD_LAUNCH
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
+}
+
+// ---- attention dropout: hicgat_gat_agg_fwd with each alpha_ij multiplied by its keep factor ------
+extern "C" int hicgat_gat_agg_drop_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
+                                       int row_begin, int row_end, const float *h, const float *a_src,
+                                       const float *a_dst, const float *bias, float neg_slope, int act, float *out,
+                                       float *out2, float *row_stats, double p, uint64_t seed,
+                                       const int64_t *step_counter, int64_t step_value, uint32_t site,
+                                       hicgat_stream_t stream) {
+  if (N < 0 || nnz < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
+  if (act != 0 && act != 1) return HICGAT_EINVAL;
+  if (!p_ok(p) || !attn_site_ok(site) || misaligned(step_counter, 8)) return HICGAT_EINVAL;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
+  if (row_end == row_begin) return HICGAT_OK;
+  if (!rowptr || !col || !h || !a_src || !a_dst || !bias || !out || !row_stats) return HICGAT_EINVAL;
+  const AttnMaskArgs mk = attn_mask_args(p, seed, step_counter, step_value, site);
+  hipStream_t s = (hipStream_t)stream;
+  if (H != 2 || C != 256)
+    return agg_fwd_drop_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act,
+                                       out, out2, row_stats, mk, s);
+  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+#define HICGAT_FWD_LAUNCH(TR, AC)                                                                             \
+  hipLaunchKernelGGL((agg_fwd_drop_h2c256_kernel<TR, AC>), grid, block, 0, s, rowptr, col, row_begin, row_end, \
+                     h, a_src, a_dst, bias, neg_slope, out, out2, row_stats, mk)
+  if (out2) {
+    if (act) HICGAT_FWD_LAUNCH(true, 1);
+    else HICGAT_FWD_LAUNCH(true, 0);
+  } else {
+    if (act) HICGAT_FWD_LAUNCH(false, 1);
+    else HICGAT_FWD_LAUNCH(false, 0);
+  }
+#undef HICGAT_FWD_LAUNCH
+  HICGAT_CHECK_LAUNCH();
+  return HICGAT_OK;
+}
+
+extern "C" int hicgat_gat_attn_mask(const int32_t *rowptr, const int32_t *col, int N, int H, double p, uint64_t seed,
+                                    const int64_t *step_counter, int64_t step_value, uint32_t site, uint8_t *mask,
+                                    hicgat_stream_t stream) {
+  if (N < 0 || !p_ok(p) || !attn_site_ok(site) || misaligned(step_counter, 8)) return HICGAT_EINVAL;
+  if (H < 1 || H > 4) return HICGAT_EUNSUPPORTED;
+  if (N == 0) return HICGAT_OK;
+  if (!rowptr || !col || !mask) return HICGAT_EINVAL;
+  return attn_mask_launch(rowptr, col, N, H, attn_mask_args(p, seed, step_counter, step_value, site), mask,
+                          (hipStream_t)stream);
 }

@@ -59,6 +59,41 @@ __global__ __launch_bounds__(256) void agg_bwd_src_generic_kernel(
                                da_src);
 }
 
+// ---- attention dropout: the DROP forms of the forward and the source pass (gat_agg.hpp), kernels of
+// their own so that the ones above keep their arguments and code.
+template <int H, int C, bool TRAIN, int ACT>
+__global__ __launch_bounds__(256) void agg_fwd_drop_generic_kernel(
+    const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
+    const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
+    const float *__restrict__ bias, float ns, float *__restrict__ out, float *__restrict__ out2,
+    float *__restrict__ row_stats, AttnMaskArgs mk) {
+  const int i = row_begin + xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_in_block();
+  if (i >= row_end) return;
+  agg_fwd_row<H, C, TRAIN, ACT, false, true>(i, rowptr, col, nullptr, nullptr, h, a_src, a_dst, bias, ns, out, out2,
+                                             row_stats, mk);
+}
+
+template <int H, int C, bool REMAP>
+__global__ __launch_bounds__(256) void agg_bwd_src_drop_generic_kernel(
+    const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
+    const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
+    const float *__restrict__ row_stats, int64_t ldr, const float *__restrict__ dout, int64_t ldq,
+    const float *__restrict__ att_s, const float *__restrict__ att_d, float ns,
+    float *__restrict__ dh, float *__restrict__ da_src, AttnMaskArgs mk) {
+  const int r = row_begin + (REMAP ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x) * 4 + wave_in_block();
+  if (r >= row_end) return;
+  agg_bwd_src_row<H, C, false, true>(r, rowptr, col, h, a_src, a_dst, row_stats, ldr, dout, ldq, att_s, att_d, ns, dh,
+                                     da_src, mk);
+}
+
+template <int H>
+__global__ __launch_bounds__(256) void attn_mask_kernel(const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                        int N, AttnMaskArgs mk, uint8_t *__restrict__ mask) {
+  const int i = blockIdx.x * 4 + wave_in_block();
+  if (i >= N) return;
+  attn_mask_row<H>(i, rowptr, col, mk, mask);
+}
+
 // every supported (H, C) but (2, 256)
 #define HICGAT_GAT_SHAPES(X) X(1, 256) X(1, 512) X(1, 768) X(1, 1024) X(2, 128) X(2, 384) X(2, 512) X(3, 256) \
   X(4, 128) X(4, 256)
@@ -148,6 +183,68 @@ int agg_bwd_src_generic_launch(const int *rowptr, const int *col, int H, int C, 
 #undef HICGAT_SRC_CASE
 #undef HICGAT_SRC_G
   return HICGAT_EUNSUPPORTED;
+}
+
+int agg_fwd_drop_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
+                                const float *h, const float *a_src, const float *a_dst, const float *bias, float ns,
+                                int act, float *out, float *out2, float *row_stats, const AttnMaskArgs &mk,
+                                hipStream_t s) {
+  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+#define HICGAT_FWD_G(TR_, AC_, H_, C_)                                                                            \
+  hipLaunchKernelGGL((agg_fwd_drop_generic_kernel<H_, C_, TR_, AC_>), grid, block, 0, s, rowptr, col, row_begin, \
+                     row_end, h, a_src, a_dst, bias, ns, out, out2, row_stats, mk)
+#define HICGAT_FWD_CASE(H_, C_)                 \
+  if (H == H_ && C == C_) {                     \
+    if (out2) {                                 \
+      if (act) HICGAT_FWD_G(true, 1, H_, C_);   \
+      else HICGAT_FWD_G(true, 0, H_, C_);       \
+    } else {                                    \
+      if (act) HICGAT_FWD_G(false, 1, H_, C_);  \
+      else HICGAT_FWD_G(false, 0, H_, C_);      \
+    }                                           \
+    HICGAT_CHECK_LAUNCH();                      \
+    return HICGAT_OK;                           \
+  }
+  HICGAT_GAT_SHAPES(HICGAT_FWD_CASE)
+#undef HICGAT_FWD_CASE
+#undef HICGAT_FWD_G
+  return HICGAT_EUNSUPPORTED;
+}
+
+int agg_bwd_src_drop_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
+                                    const float *h, const float *a_src, const float *a_dst, const float *row_stats,
+                                    int64_t ldr, const float *dout, int64_t ldq4, const float *att_s,
+                                    const float *att_d, float ns, float *dh, float *da_src, bool remap,
+                                    const AttnMaskArgs &mk, hipStream_t s) {
+  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+#define HICGAT_SRC_G(RM_, H_, C_)                                                                                \
+  hipLaunchKernelGGL((agg_bwd_src_drop_generic_kernel<H_, C_, RM_>), grid, block, 0, s, rowptr, col, row_begin,  \
+                     row_end, h, a_src, a_dst, row_stats, ldr, dout, ldq4, att_s, att_d, ns, dh, da_src, mk)
+#define HICGAT_SRC_CASE(H_, C_)            \
+  if (H == H_ && C == C_) {                \
+    if (remap) HICGAT_SRC_G(true, H_, C_); \
+    else HICGAT_SRC_G(false, H_, C_);      \
+    HICGAT_CHECK_LAUNCH();                 \
+    return HICGAT_OK;                      \
+  }
+  HICGAT_GAT_SHAPES(HICGAT_SRC_CASE)
+#undef HICGAT_SRC_CASE
+#undef HICGAT_SRC_G
+  return HICGAT_EUNSUPPORTED;
+}
+
+int attn_mask_launch(const int *rowptr, const int *col, int N, int H, const AttnMaskArgs &mk, uint8_t *mask,
+                     hipStream_t s) {
+  const dim3 grid((N + 3) / 4), block(256);
+  switch (H) {
+    case 1: hipLaunchKernelGGL(attn_mask_kernel<1>, grid, block, 0, s, rowptr, col, N, mk, mask); break;
+    case 2: hipLaunchKernelGGL(attn_mask_kernel<2>, grid, block, 0, s, rowptr, col, N, mk, mask); break;
+    case 3: hipLaunchKernelGGL(attn_mask_kernel<3>, grid, block, 0, s, rowptr, col, N, mk, mask); break;
+    case 4: hipLaunchKernelGGL(attn_mask_kernel<4>, grid, block, 0, s, rowptr, col, N, mk, mask); break;
+    default: return HICGAT_EUNSUPPORTED;
+  }
+  HICGAT_CHECK_LAUNCH();
+  return HICGAT_OK;
 }
 
 }  // namespace hicgat

@@ -1,6 +1,7 @@
 // The counter-based keep mask of feature dropout (include/hicgat.h "feature dropout"), shared by
 // dropout.hip and batchnorm.hip: Philox4x32-10 over (global row, column quad, step, site) keyed by
-// the seed, and the host-side threshold / scale of a drop probability.
+// the seed, and the host-side threshold / scale of a drop probability.  Also the per-(edge, head)
+// mask of attention dropout (gat_agg.hpp's DROP forms): the same generator over (i, j, step, site).
 #pragma once
 #include "common.hpp"
 
@@ -41,6 +42,45 @@ __device__ __forceinline__ uint4 quad_words(const MaskArgs &m, uint32_t step, in
                        (uint32_t)(m.seed >> 32));
 }
 
+// ---- attention dropout (include/hicgat.h "attention dropout"): one keep bit per (edge, head), a
+// pure function of (seed, step, site, destination row i, source row j, head).  One Philox call per
+// edge, counter (i, j, step, site | kAttnSiteBit); head hh uses output word hh (H <= 4).  i and j are
+// global node ids, so the source pass recomputes the bits of edge (i -> r) from (col[e], r).
+constexpr uint32_t kAttnSiteBit = HICGAT_ATTN_SITE_BIT;  // keeps attention sites apart from feature-dropout sites
+
+// What a DROP launch needs to know about the mask (by value: 40 bytes of kernel arguments).
+struct AttnMaskArgs {
+  uint64_t seed;
+  const int64_t *step_counter;   // device; NULL: step_value
+  int64_t step_value;
+  uint32_t site, T;              // site with kAttnSiteBit already set
+  float scale;
+};
+
+__device__ __forceinline__ uint32_t mask_step(const AttnMaskArgs &m) {
+  return (uint32_t)(m.step_counter ? *m.step_counter : m.step_value);
+}
+
+// keep[hh] of edge (destination i, source j)
+template <int H>
+__device__ __forceinline__ void attn_keep(const AttnMaskArgs &m, uint32_t step, int i, int j, bool (&keep)[H]) {
+  static_assert(H >= 1 && H <= 4, "one Philox call serves at most four heads");
+  const uint4 r = philox4x32_10(make_uint4((uint32_t)i, (uint32_t)j, step, m.site), (uint32_t)m.seed,
+                                (uint32_t)(m.seed >> 32));
+  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+  for (int hh = 0; hh < H; ++hh) keep[hh] = w[hh] >= m.T;
+}
+
+// the factor m_ij in {0, scale} that multiplies alpha_ij, per head
+template <int H>
+__device__ __forceinline__ void attn_factor(const AttnMaskArgs &m, uint32_t step, int i, int j, float (&f)[H]) {
+  bool keep[H];
+  attn_keep<H>(m, step, i, j, keep);
+#pragma unroll
+  for (int hh = 0; hh < H; ++hh) f[hh] = keep[hh] ? m.scale : 0.f;
+}
+
 template <int ACT>
 __device__ __forceinline__ float act_apply(float x, float slope) {
   if (ACT == HICGAT_ACT_RELU) return relu_t(x);
@@ -66,6 +106,14 @@ inline uint32_t keep_threshold(double p) {
 }
 
 inline float keep_scale(double p) { return (float)(1.0 / (1.0 - p)); }
+
+// attention dropout: the caller's site must leave kAttnSiteBit free (site < 2^31)
+inline bool attn_site_ok(uint32_t site) { return (site & kAttnSiteBit) == 0; }
+
+inline AttnMaskArgs attn_mask_args(double p, uint64_t seed, const int64_t *step_counter, int64_t step_value,
+                                   uint32_t site) {
+  return AttnMaskArgs{seed, step_counter, step_value, site | kAttnSiteBit, keep_threshold(p), keep_scale(p)};
+}
 
 inline bool misaligned(const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; }
 

@@ -1,7 +1,8 @@
 """hicgat -- the GAT-HiC per-epoch hot path on MI355X (gfx950) HIP kernels.
 
 Drop-in surface of the reference (beyzoskaya/HiC-GNN):
-  hicgat.nn.GATConv                           ~ torch_geometric.nn.GATConv (PyG 1.7.2)
+  hicgat.nn.GATConv                           ~ torch_geometric.nn.GATConv (PyG 1.7.2), dropout=p (on the
+                                                attention coefficients) included
   hicgat.nn.SAGEConv                          ~ layers.SAGEConv (layers.py:12-79)
   hicgat.gat_models.GATNetSelectiveResidualsUpdated / GATNetHeadsChanged3LayersLeakyReLUv2 / Net
                                               ~ models.py:614-691 / :1010-1047 / :14-55
@@ -22,6 +23,7 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
   hicgat.ops.act                              ~ F.gelu / F.leaky_relu
   hicgat.ops.bn_act_dropout                   ~ torch.nn.BatchNorm1d -> F.leaky_relu -> torch.nn.Dropout(p)
   hicgat.ops.act_dropout, hicgat.DropoutState ~ x.relu() / F.leaky_relu(x) -> torch.nn.Dropout(p)
+  hicgat.ops.attention_dropout_mask           ~ the keep mask of GATConv(dropout=p) (tests, tools)
   hicgat.graph.load_input / cont2dist / convert_to_matrix / Adj
                                               ~ utils.py:10-80 (+ torch_sparse.SparseTensor)
   hicgat.train.train / main                   ~ HiC-GNN_main.py:107-160

@@ -57,6 +57,12 @@ SIGNATURES = {
                                         c_i64, c_p, c_p]),
     "hicgat_gat_agg_bwd_src": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
                                        c_i64, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_int, c_p]),
+    "hicgat_gat_agg_drop_fwd": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p,
+                                        c_p, c_f, c_int, c_p, c_p, c_p, c_d, c_u64, c_p, c_i64, c_u32, c_p]),
+    "hicgat_gat_agg_drop_bwd_src": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
+                                            c_i64, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_int, c_d, c_u64, c_p,
+                                            c_i64, c_u32, c_p]),
+    "hicgat_gat_attn_mask": (c_int, [c_p, c_p, c_int, c_int, c_d, c_u64, c_p, c_i64, c_u32, c_p, c_p]),
     "hicgat_gat_agg_fwd_tiled": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int,
                                          c_int, c_p, c_p, c_p, c_p, c_f, c_int, c_p, c_p, c_p, c_int, c_p, c_sz,
                                          c_p]),

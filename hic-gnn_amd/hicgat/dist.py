@@ -398,6 +398,11 @@ class ShardedTrainer:
             # the sharded step runs model.tail / post_act on its own rows: it would train without dropout
             raise NotImplementedError(f"ShardedTrainer does not run feature dropout; {type(model).__name__} trains "
                                       f"with Dropout at {model.drop_sites} sites (single-GPU hicgat.train only)")
+        if float(getattr(conv, "dropout", 0.0) or 0.0) != 0.0:
+            # before any collective: the sharded forms (gat_xagg.hip, the slab source pass) have no DROP form
+            # and would train without the dropout
+            raise NotImplementedError(f"ShardedTrainer does not run attention dropout; {type(model).__name__}.conv "
+                                      f"has dropout = {conv.dropout} (single-GPU hicgat.train only)")
         if kern is None:
             from .kernels import default
             kern = default()

@@ -186,6 +186,46 @@ class HipKernels:
                                                        _lib.stream(h.device)),
                        "hicgat_gat_agg_bwd_src")
 
+    # -- attention dropout (include/hicgat.h "attention dropout"): the DROP forms of the two gathers --
+    # ``drop`` = (p, seed, step_ctr, step_value, site): the step comes from the device count
+    # ``step_ctr`` (int64 [1]) or, if that is None, from ``step_value``
+    def agg_drop_fwd(self, rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, act, out, out2, row_stats, drop):
+        """``agg_fwd_act`` with every alpha multiplied by its keep factor (out, out2; not S3)."""
+        N = h.shape[0]
+        H = a_src.shape[1]
+        C = h.shape[1] // H
+        p, seed, step_ctr, step_value, site = drop
+        with _timed("gat_agg_drop_fwd"):
+            _lib.check(self.lib.hicgat_gat_agg_drop_fwd(P(rowptr), P(col), N, col.numel(), H, C, r0, r1, P(h),
+                                                        P(a_src), P(a_dst), P(bias), float(ns), int(act), P(out),
+                                                        P(out2), P(row_stats), float(p), int(seed), P(step_ctr),
+                                                        int(step_value), int(site), _lib.stream(h.device)),
+                       "hicgat_gat_agg_drop_fwd")
+
+    def agg_drop_bwd_src(self, rowptr, col, r0, r1, h, a_src, a_dst, row_stats, dout, att_l, att_r, ns, dh, da_src,
+                         drop, round_robin=False):
+        """``agg_bwd_src`` with the forward's keep factors recomputed from (col[e], r)."""
+        N = h.shape[0]
+        H = a_src.shape[1]
+        C = h.shape[1] // H
+        assert row_stats.stride(1) == 1 and dout.stride(1) == 1
+        p, seed, step_ctr, step_value, site = drop
+        with _timed("gat_agg_drop_bwd_src"):
+            _lib.check(self.lib.hicgat_gat_agg_drop_bwd_src(
+                P(rowptr), P(col), N, H, C, r0, r1, P(h), P(a_src), P(a_dst), P(row_stats), row_stats.stride(0),
+                P(dout), dout.stride(0), P(att_l), P(att_r), float(ns), P(dh), P(da_src),
+                self.SRC_ROUND_ROBIN if round_robin else 0, float(p), int(seed), P(step_ctr), int(step_value),
+                int(site), _lib.stream(h.device)), "hicgat_gat_agg_drop_bwd_src")
+
+    def attn_mask(self, rowptr, col, H, mask, drop):
+        """The keep bits of every (edge, head) into ``mask`` (contiguous uint8 [nnz, H])."""
+        assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape == (col.numel(), H)
+        p, seed, step_ctr, step_value, site = drop
+        _lib.check(self.lib.hicgat_gat_attn_mask(P(rowptr), P(col), rowptr.numel() - 1, int(H), float(p), int(seed),
+                                                 P(step_ctr), int(step_value), int(site), P(mask),
+                                                 _lib.stream(mask.device)), "hicgat_gat_attn_mask")
+        return mask
+
     def param_grad(self, h, dout, da_src, row_stats, H, out=None, accumulate=False):
         """Column sums over the given rows -> (datt_src [D], datt_dst [D], dbias [D]); ``out`` =
         three destination tensors (e.g. the parameters' own .grad views) to write or add into; a

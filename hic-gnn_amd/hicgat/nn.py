@@ -7,6 +7,11 @@ in the state_dict exactly like PyG), ``att_l`` / ``att_r`` [1, H, C], ``bias`` [
 draws of the initialisation follow PyG 1.7.2 (``torch.nn.Linear``'s own init, then glorot on
 lin_l, glorot on lin_r (the same tensor), glorot on att_l, att_r, zeros on bias), so
 ``torch.manual_seed(s)`` gives the reference's initial weights bit for bit.
+
+``dropout`` = p in [0, 1) is PyG's dropout on the attention coefficients: in training mode every
+alpha_ij is multiplied by a keep factor in {0, 1 / (1 - p)} per head inside the aggregation kernels
+(DESIGN.md "Attention dropout").  It adds no parameter, buffer or RNG draw.  Out of scope (refused):
+``concat=False``, ``add_self_loops=False``, bipartite inputs.
 """
 import math
 
@@ -14,6 +19,7 @@ import torch
 from torch.nn import Linear, Parameter
 
 from . import ops
+from .dropout import check_p
 
 
 def _glorot(t):
@@ -30,8 +36,7 @@ class GATConv(torch.nn.Module):
             raise NotImplementedError("bipartite (tuple) in_channels is out of scope")
         if not concat:
             raise NotImplementedError("concat=False (head mean) is out of scope")
-        if dropout != 0.0:
-            raise NotImplementedError("attention dropout > 0 is out of scope (the reference uses 0)")
+        dropout = check_p(dropout)
         if not add_self_loops:
             raise NotImplementedError("add_self_loops=False is out of scope")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
@@ -56,18 +61,42 @@ class GATConv(torch.nn.Module):
             with torch.no_grad():
                 self.bias.zero_()
 
-    def forward(self, x, edge_index, act=None, return_attention_weights=None):
+    def dropout_state(self, device):
+        """The conv's own ``DropoutState`` (made on first use on ``device``, seed ``torch.initial_seed()``:
+        read, not drawn)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        st = getattr(self, "_dropout_state", None)
+        if st is None or st.device != device:
+            from .dropout import DropoutState
+            st = self._dropout_state = DropoutState(device)
+        return st
+
+    def forward(self, x, edge_index, act=None, return_attention_weights=None, dropout_state=None, site=0):
         """``edge_index`` is a ``hicgat.graph.Adj`` (the reference passes a SparseTensor).
+        In training mode with ``self.dropout`` > 0 (read here, so it may be set on the module as in PyG)
+        the attention coefficients are dropped; the returned attention weights are the undropped ones,
+        as PyG's.  The mask comes from ``dropout_state`` (a ``DropoutState`` the caller advances once per
+        training forward, shared with its other dropout sites) and ``site``; without one the conv owns
+        a state and advances it itself, first in the forward.
         ``act="relu"`` (not in PyG) returns relu(forward(x)) with the relu fused into the kernel.
         ``return_attention_weights=True`` returns ``(out, attn)`` as PyG does for a SparseTensor input
         (``edge_index.set_value(alpha, layout='coo')``): ``attn`` is an ``Adj`` over the self-looped CSR
         whose ``storage.rowptr()`` / ``col()`` are int64 and whose ``storage.value()`` is alpha [nnz, H],
         attached to autograd (a loss may depend on it)."""
+        drop = {}
+        p = check_p(self.dropout)
+        if self.training and p > 0.0:
+            if dropout_state is None:
+                dropout_state = self.dropout_state(x.device)
+                dropout_state.advance()
+            drop = dict(dropout=p, training=True, state=dropout_state, site=site)
         if not return_attention_weights:
             return ops.gat_conv(x, self.lin_l.weight, self.att_l, self.att_r, self.bias, edge_index,
-                                self.negative_slope, act)
+                                self.negative_slope, act, **drop)
         out, alpha = ops.gat_conv(x, self.lin_l.weight, self.att_l, self.att_r, self.bias, edge_index,
-                                  self.negative_slope, act, return_attention_weights=True)
+                                  self.negative_slope, act, return_attention_weights=True, **drop)
         return out, edge_index.with_self_loops(alpha)
 
     def __repr__(self):

@@ -49,8 +49,10 @@ class _GATConvFn(torch.autograd.Function):
     is a streaming pass (``agg_bwd_rows``) and only the source half gathers."""
 
     @staticmethod
-    def forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, tiles=None, tmap=None):
-        # tmap: only from _GATConvAttnFn, which runs this body and then adds the attention weights
+    def forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, tiles=None, tmap=None, drop=None):
+        # tmap: only from _GATConvAttnFn / _GATConvDropFn, which run this body and then add the attention
+        # weights; drop: only from _GATConvDropFn, the (p, seed, step_ctr, step_value, site) of
+        # kernels.agg_drop_fwd -- attention dropout in the two gathers (never with tiles)
         _lib.lib()
         _dev_check(x, W, att_l, att_r, bias, rowptr, col)
         K = kernels.default()
@@ -67,11 +69,14 @@ class _GATConvFn(torch.autograd.Function):
         row_stats = torch.empty((N, 4 * H), dtype=torch.float32, device=x.device)
         train = any(ctx.needs_input_grad[:5])
         out2 = torch.empty((N, D), dtype=torch.float32, device=x.device) if train else None
-        if tiles is not None:
+        if drop is not None:
+            K.agg_drop_fwd(rowptr, col, 0, N, h, a_src, a_dst, b, negative_slope, act, out, out2, row_stats, drop)
+        elif tiles is not None:
             K.agg_fwd_tiled(rowptr, col, tiles, h, a_src, a_dst, b, negative_slope, act, out, out2, row_stats)
         else:
             K.agg_fwd_act(rowptr, col, 0, N, h, a_src, a_dst, b, negative_slope, act, out, out2, row_stats)
         ctx.tiles = tiles
+        ctx.drop = drop
         ctx.rows_state = None
         if train:
             ctx.save_for_backward(x, W, al, ar, h, a_src, a_dst, row_stats, rowptr, col, out, out2, b)
@@ -122,7 +127,12 @@ class _GATConvFn(torch.autograd.Function):
         pW, pl, pr, pb = ctx.params
         sinks = (_sink(pl), _sink(pr), _sink(pb) if ctx.has_bias else None)
         use_sinks = all(t is not None for t in sinks)
-        if ctx.tiles is not None:
+        if ctx.drop is not None:
+            streams.stamp("src_begin")
+            K.agg_drop_bwd_src(rowptr, col, 0, N, h, a_src, a_dst, row_stats, dout, al, ar, ctx.ns, dh, da_src,
+                               ctx.drop)
+            streams.stamp("src_end")
+        elif ctx.tiles is not None:
             K.agg_bwd_src_tiled(ctx.tiles, h, a_src, a_dst, row_stats, dout, al, ar, ctx.ns, dh, da_src)
         else:
             streams.stamp("src_begin")
@@ -182,6 +192,31 @@ class _GATConvAttnFn(torch.autograd.Function):
             dout = torch.zeros_like(ctx.saved_tensors[10])
         G = None if dalpha is None else dalpha.contiguous().float()
         return _GATConvFn.backward(ctx, dout, G) + (None,)
+
+
+class _GATConvDropFn(torch.autograd.Function):
+    """``_GATConvFn`` with attention dropout (PyG's ``F.dropout(alpha, p, training)`` in ``message``): the
+    DROP forms of the forward gather and of the source pass, the gather form at every shape (no tiles),
+    the rows pass and its fused-tail link as they are.  The forward keeps its own copy of the state's
+    step count, so its backward regenerates the forward's mask whatever the state has counted since.
+    With a ``tmap`` it also returns alpha [nnz, H] -- the pre-dropout softmax, as PyG's ``_alpha`` -- and
+    takes (dout, dalpha) like ``_GATConvAttnFn``; dalpha's share sees no mask."""
+
+    @staticmethod
+    def forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, tmap, p, state, site):
+        ctx.set_materialize_grads(False)
+        _dev_check(x, state.counter)
+        drop = (p, state.seed, state.counter.clone(), 0, site)
+        return _GATConvFn.forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, None, tmap, drop)
+
+    @staticmethod
+    def backward(ctx, dout, dalpha=None):
+        if dout is None:
+            if dalpha is None:
+                return (None,) * 13
+            dout = torch.zeros_like(ctx.saved_tensors[10])
+        G = None if dalpha is None else dalpha.contiguous().float()
+        return _GATConvFn.backward(ctx, dout, G) + (None,) * 3
 
 
 def attention_entropy(alpha):
@@ -376,6 +411,19 @@ def dropout_mask(rows, W, p, seed, step, site, row_offset=0, device="cuda"):
         raise _lib.HicgatUnavailable("hicgat ops need a CUDA (HIP) device; got " + str(device))
     m = torch.empty((int(rows), int(W)), dtype=torch.uint8, device=device)
     kernels.default().dropout_mask(m, p, int(seed) & ((1 << 64) - 1), None, int(step), site, row_offset)
+    return m.bool()
+
+
+def attention_dropout_mask(adj, H, p, seed, step, site):
+    """The keep mask (bool [nnz, H], self-looped CSR order: ``adj.rowptr32`` / ``adj.col32``) that
+    attention dropout uses for these arguments (tests, tools)."""
+    from .dropout import check_p
+    p = check_p(p)
+    if adj.rowptr32 is None or not adj.rowptr32.is_cuda:
+        raise _lib.HicgatUnavailable("attention_dropout_mask needs an Adj on a CUDA (HIP) device")
+    m = torch.empty((adj.col32.numel(), int(H)), dtype=torch.uint8, device=adj.col32.device)
+    kernels.default().attn_mask(adj.rowptr32, adj.col32, int(H), m,
+                                (p, int(seed) & ((1 << 64) - 1), None, int(step), _attn_site(site)))
     return m.bool()
 
 
@@ -1000,6 +1048,9 @@ def prepacked(model, job):
 GAT_SHAPE_RULE = "out_channels % 128 == 0, heads * out_channels a multiple of 256 and <= 1024, heads <= 4"
 
 
+ATTN_SITE_LIMIT = 1 << 31   # include/hicgat.h HICGAT_ATTN_SITE_BIT: attention-dropout sites lie below it
+
+
 def gat_shape_supported(H, C):
     """Whether the aggregation kernels run GATConv(heads=H, out_channels=C) (include/hicgat.h; the
     rule of gat_generic.hip, usable without the library loaded)."""
@@ -1007,10 +1058,25 @@ def gat_shape_supported(H, C):
     return 1 <= H <= 4 and C > 0 and C % 128 == 0 and (H * C) % 256 == 0 and H * C <= 1024
 
 
-def gat_conv(x, W, att_l, att_r, bias, adj, negative_slope=0.2, act=None, return_attention_weights=False):
+def _attn_site(site):
+    site = int(site)
+    if not 0 <= site < ATTN_SITE_LIMIT:
+        raise ValueError(f"an attention-dropout site must satisfy 0 <= site < 2**31, got {site}")
+    return site
+
+
+def gat_conv(x, W, att_l, att_r, bias, adj, negative_slope=0.2, act=None, return_attention_weights=False,
+             dropout=0.0, training=False, state=None, site=0):
     """GATConv forward; ``act="relu"`` returns relu(GATConv(x)) with the relu fused.
     ``return_attention_weights=True`` returns ``(out, alpha)``: alpha [nnz, H] in the order of the
-    self-looped device CSR (``adj.rowptr32`` / ``adj.col32``), attached to autograd."""
+    self-looped device CSR (``adj.rowptr32`` / ``adj.col32``), attached to autograd.
+    ``dropout`` = p with ``training``: attention dropout, every alpha_ij times its keep factor in
+    {0, 1 / (1 - p)} per head, with the mask of (state.seed, the state's device step count, site, i, j,
+    head) (``state``: a ``dropout.DropoutState`` the caller has advanced; ``attention_dropout_mask``);
+    it follows ``training``, not the grad mode, and alpha is returned as it was before the dropout.
+    Without ``training`` or with p = 0 the call is the plain one."""
+    from .dropout import check_p
+    p = check_p(dropout)
     H, C = att_l.shape[-2], att_l.shape[-1]
     if not gat_shape_supported(H, C):
         raise NotImplementedError(f"GATConv(heads={H}, out_channels={C}) is not supported by the aggregation "
@@ -1018,6 +1084,14 @@ def gat_conv(x, W, att_l, att_r, bias, adj, negative_slope=0.2, act=None, return
     if adj.rowptr32 is None or adj.rowptr32.device != x.device:
         adj.to(x.device)
     # the matrix-core tiled form (gat_tiles.hip) is (2, 256) only: every other shape gathers
+    if training and p > 0.0:
+        if state is None:
+            raise ValueError("gat_conv(dropout > 0, training=True) needs a DropoutState")
+        site = _attn_site(site)
+        _dev_check(x, W, att_l, att_r, bias)
+        tmap = adj.transpose_map() if return_attention_weights else None
+        return _GATConvDropFn.apply(x, W, att_l, att_r, bias, adj.rowptr32, adj.col32, negative_slope, _ACTS[act],
+                                    tmap, p, state, site)
     tiles = adj.tiles() if (H, C) == (2, 256) else None
     if return_attention_weights:
         return _GATConvAttnFn.apply(x, W, att_l, att_r, bias, adj.rowptr32, adj.col32, negative_slope, _ACTS[act],

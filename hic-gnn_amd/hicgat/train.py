@@ -47,7 +47,8 @@ LOSSES = ("mse", "combined", "contrastive", "mse+dscc")
 
 
 def train(model, data, truth, lr=1e-3, thresh=1e-8, steps=None, loss="mse", max_steps=1_000_000,
-          on_step=None, graph=None, dscc_history=None, print_interval=0, alpha=1.0, mse_history=None):
+          on_step=None, graph=None, dscc_history=None, print_interval=0, alpha=1.0, mse_history=None,
+          attn_dropout=0.0):
     """Returns (optimizer, per-step loss list).  ``truth`` is a ``graph.Truth``.
 
     ``graph`` (default: on for device tensors): after ``GRAPH_WARMUP`` eager steps the step is
@@ -64,8 +65,18 @@ def train(model, data, truth, lr=1e-3, thresh=1e-8, steps=None, loss="mse", max_
     (the Spearman term is detached there too), rho is scored on ``model.get_model``'s coordinates
     (:132-133: the step's own for a model without dropout sites, a second no-grad forward for a
     ``_DropoutMLP``); fixed ``steps`` gives the script's epoch loop.  ``dscc_history`` then receives
-    each step's rho and ``mse_history`` (a list) the MSE part."""
+    each step's rho and ``mse_history`` (a list) the MSE part.
+
+    ``attn_dropout`` = p > 0 sets ``model.conv.dropout`` (PyG's GATConv(dropout=p): dropout on the
+    attention coefficients in training mode; 0 leaves the model as it is).  The conv's own
+    ``DropoutState`` is made by the first eager step, so the captured step replays as the next step."""
     from .graphs import CapturedStep
+    from .dropout import check_p
+    from .nn import GATConv
+    if check_p(attn_dropout) > 0.0:
+        if not isinstance(getattr(model, "conv", None), GATConv):
+            raise ValueError(f"attn_dropout needs a model whose ``conv`` is a GATConv; {type(model).__name__} has none")
+        model.conv.dropout = check_p(attn_dropout)
     if loss not in LOSSES:       # a KeyError, as ops.LOSS_KINDS[kind] raises for the fused kinds
         raise KeyError(f"unknown loss {loss!r}: one of {', '.join(LOSSES)}")
     with_dscc = loss == "mse+dscc"
@@ -155,6 +166,9 @@ def make_parser():
     p.add_argument("--loss", default="mse", choices=list(LOSSES))
     p.add_argument("--alpha", type=float, default=1.0, help="weight of the (1 - dSCC) term of --loss mse+dscc "
                                                             "(combined_loss_training.py:142)")
+    p.add_argument("--attn-dropout", type=float, default=0.0, metavar="P",
+                   help="dropout on the GATConv's attention coefficients while training (PyG's "
+                        "GATConv(dropout=P)); 0: none")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", default=None, help="prefix for <out>_weights.pt / _structure.pdb / _log.txt")
     p.add_argument("--no-kr", action="store_true", help="the input is already KR-normalised (skip KRnorm)")
@@ -195,6 +209,8 @@ def main(argv=None):
         print(f"Training model using conversion value {f}.")
         model = model_class(a.model)().to(data.x.device)
         extra = {"alpha": a.alpha} if a.loss == "mse+dscc" else {}
+        if a.attn_dropout:
+            extra["attn_dropout"] = a.attn_dropout
         _, hist = train(model, data, truth, a.learningrate, a.threshold, a.steps, a.loss, **extra)
         coords = model.get_model(data.x.float(), data.edge_index).detach()
         rho = metrics.dscc(coords, truth.scoring())

@@ -134,6 +134,53 @@ int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int
                            const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
                            const float *att_src, const float *att_dst, float neg_slope, float *dh, float *da_src,
                            int flags, hicgat_stream_t stream);
+/* ---- attention dropout: PyG 1.7.2 GATConv(dropout=p), `alpha = F.dropout(alpha, p, training)` in
+ * message(), inside the two gathering passes -------------------------------------------------------
+ * Every alpha_ij of the forward is multiplied, per head, by m_ij in {0, scale}; the softmax itself
+ * (row_stats max / sum, hicgat_gat_alpha) is that of the undropped row, and self loops are dropped
+ * like any other edge.  The mask is a pure function of (seed, step, site, destination row i, source
+ * row j, head), with i and j GLOBAL node ids, so it depends neither on the launch geometry, nor on
+ * the row range, nor on the edge's position -- the source pass recomputes the bits of edge (i -> r)
+ * from (col[e], r) and no [nnz, H] tensor exists.  Philox4x32-10 as under "feature dropout" below:
+ *   counter = (i, j, step & 0xffffffff, site | HICGAT_ATTN_SITE_BIT);  key = (seed & 0xffffffff, seed >> 32);
+ *   head hh uses output word r[hh] (H <= 4: one call per edge);  kept iff r[hh] >= T,
+ *   T = min(floor(p * 2^32), 2^32 - 1);  m = kept ? scale : 0,  scale = (float)(1.0 / (1.0 - p)).
+ * HICGAT_ATTN_SITE_BIT keeps these sites apart from the feature-dropout sites that share a seed and a
+ * step count; the caller's site must be < 2^31.  step = *step_counter when the pointer is given (a
+ * device int64, 8-B aligned; NULL-able), else step_value.
+ *   hicgat_gat_agg_drop_fwd: hicgat_gat_agg_fwd with  out[i] = sum_j alpha_ij m_ij h[j] + bias  (then
+ *     relu, act = 1),  out2[i] = sum_j alpha_ij lrelu'(e_ij) m_ij h[j]  (masked) and
+ *     S3[i] = sum_j alpha_ij lrelu'(e_ij)  (NOT masked).  out2 NULL-able as there.
+ *   hicgat_gat_agg_bwd_rows is unchanged: delta_i = <dout_i, out_i - bias> = sum_k alpha_ik m_ik g_ik and
+ *     da_dst_i = <dout_i, out2_i> - delta_i S3_i are the dropped layer's.
+ *   hicgat_gat_agg_drop_bwd_src: hicgat_gat_agg_bwd_src with
+ *     dh[r] = sum_i alpha_ir m_ir dout[i] + da_src[r] (x) att_l + da_dst[r] (x) att_r,
+ *     da_src[r] = <sum_i alpha_ir s_ir m_ir dout_i, h_r> - sum_i alpha_ir s_ir delta_i   (s = lrelu').
+ *   hicgat_gat_attn_mask: mask[e * H + hh] = kept ? 1 : 0 (uint8 [nnz, H], self-looped CSR order) from
+ *     the same device function (tests, tools); 1 <= H <= 4, else HICGAT_EUNSUPPORTED.
+ * A gradient that arrives through alpha itself (hicgat_gat_alpha_bwd_*) sees no mask: PyG returns the
+ * pre-dropout alpha.  Checked before any launch: p outside [0, 1) or NaN, site >= 2^31, a misaligned
+ * step_counter and everything hicgat_gat_agg_fwd / _bwd_src refuse -> HICGAT_EINVAL; an unsupported
+ * (H, C) -> HICGAT_EUNSUPPORTED; an empty row range (N == 0 for the mask) is a no-op.  p = 0 keeps
+ * everything (scale 1).  The tiled (hicgat_gat_agg_*_tiled), aggregate-first (hicgat_xagg_*) and
+ * stand-alone destination (hicgat_gat_agg_bwd_dst) forms have no dropout. */
+#define HICGAT_ATTN_SITE_BIT 0x80000000u
+enum { HICGAT_ATTN_SITE_MAX = 0x7fffffff };   /* the largest site a caller may pass */
+int hicgat_gat_agg_drop_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
+                            int row_begin, int row_end, const float *h, const float *a_src, const float *a_dst,
+                            const float *bias, float neg_slope, int act, float *out, float *out2, float *row_stats,
+                            double p, uint64_t seed, const int64_t *step_counter, int64_t step_value, uint32_t site,
+                            hicgat_stream_t stream);
+int hicgat_gat_agg_drop_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H, int C, int row_begin,
+                                int row_end, const float *h, const float *a_src, const float *a_dst,
+                                const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
+                                const float *att_src, const float *att_dst, float neg_slope, float *dh,
+                                float *da_src, int flags, double p, uint64_t seed, const int64_t *step_counter,
+                                int64_t step_value, uint32_t site, hicgat_stream_t stream);
+int hicgat_gat_attn_mask(const int32_t *rowptr, const int32_t *col, int N, int H, double p, uint64_t seed,
+                         const int64_t *step_counter, int64_t step_value, uint32_t site, uint8_t *mask,
+                         hicgat_stream_t stream);
+
 /* ---- the attention weights as an output, and their backward (gat_attn.hip) ---------------------
  * Reference: PyG 1.7.2 GATConv.forward(x, edge_index, return_attention_weights=True), which
  * models.py:1122 calls: alpha [nnz, H] in the order of the self-looped CSR, an autograd tensor there.

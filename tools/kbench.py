@@ -94,6 +94,11 @@ def main():
         "gat_agg_bwd_rows": lambda K: K.agg_bwd_rows(0, n, 1, dout, out, b, out2, dh, rs),
         "gat_agg_bwd_src": lambda K: K.agg_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, al, ar,
                                                    0.2, dh, da),
+        # attention dropout (p = 0.5, the step by value): the DROP forms of the two gathers
+        "gat_agg_drop_fwd_train": lambda K: K.agg_drop_fwd(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, b, 0.2, 1, out,
+                                                           out2, rs, (0.5, 1, None, 1, 0)),
+        "gat_agg_drop_bwd_src": lambda K: K.agg_drop_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, al,
+                                                             ar, 0.2, dh, da, (0.5, 1, None, 1, 0)),
         "param_grad": lambda K: K.param_grad(h, dout, da, rs, H),
         "pairdist_mse_fused": lambda K: K.fused_loss(coords, truth.buf, n, 0, 0, -1, stats, loss, dc),
         "pairdist_combined": lambda K: K.fused_loss(coords, truth.buf, n, 1, 0, -1, stats, loss, dc),
@@ -115,7 +120,7 @@ def main():
     }
     if not flagship:
         keep = ("gat_linear_att", "gat_agg_fwd", "gat_agg_fwd_train", "gat_agg_bwd_dst", "gat_agg_bwd_rows",
-                "gat_agg_bwd_src", "param_grad")
+                "gat_agg_bwd_src", "gat_agg_drop_fwd_train", "gat_agg_drop_bwd_src", "param_grad")
         jobs = {k: v for k, v in jobs.items() if k in keep}
     if a.only:
         keys = [k.strip() for k in a.only.split(",") if k.strip()]
