@@ -4,8 +4,9 @@
 //   agg_bwd_dst_row   destination side, stand-alone gathering form
 //   agg_bwd_src_row   source side
 //   attn_mask_row     the attention-dropout keep bits of a row's edges (tests, tools)
-// The __global__ kernels around them only pick the row: the (2, 256) entry kernels with their
-// measured launch parameters in gat_fwd.hip / gat_bwd.hip, every other shape's in gat_generic.hip.
+// The __global__ kernels around them only pick the row: per pass one (2, 256) entry kernel with its
+// measured launch parameters and one for every other shape, the forward's in gat_fwd.hip, the
+// backward's in gat_bwd.hip, launched through gat_launch.hpp's shape list.
 // Supported set:  C % 128 == 0,  D = H*C a multiple of 256,  D <= 1024,  H <= 4.
 //
 // Design: one wave per destination row, four rows per 256-thread workgroup, no [nnz, H, C] tensor,

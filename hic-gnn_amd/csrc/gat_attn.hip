@@ -14,10 +14,9 @@
 // atomics.  The backward passes read alpha as the forward wrote it (no exp) and take the slope from
 // the sign of the recomputed logit, so they move col / tmap, alpha and G once each plus row scalars.
 #include "common.hpp"
+#include "gat_launch.hpp"   // gat_shape_supported
 
 namespace hicgat {
-
-bool gat_shape_supported(int H, int C);   // gat_generic.hip
 
 namespace {
 

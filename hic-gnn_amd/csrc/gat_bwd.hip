@@ -18,13 +18,14 @@
 // transpose needs no permutation array and no atomics.
 //
 // The per-row bodies of the three passes are gat_agg.hpp's (agg_bwd_rows_row, agg_bwd_dst_row,
-// agg_bwd_src_row).  Here: the (2, 256) entry kernels with their measured launch parameters, the
-// parameter-gradient reductions, and the C ABI, which routes every other supported shape to
-// gat_generic.hip.
+// agg_bwd_src_row).  Here: their entry kernels -- for (2, 256) under the names the profiles know, with
+// measured launch parameters, and for every other supported shape -- one launch per pass (the
+// dispatcher is gat_launch.hpp's), the parameter-gradient reductions, and the C ABI.
 #include <algorithm>
 #include <cstdlib>
 
 #include "gat_agg.hpp"
+#include "gat_launch.hpp"
 
 namespace hicgat {
 
@@ -36,38 +37,48 @@ __global__ __launch_bounds__(256) void agg_bwd_dst_h2c256_kernel(
   if (i < row_end) agg_bwd_dst_row<2, 256>(i, rowptr, col, h, a_src, a_dst, dout, ns, row_stats);
 }
 
+template <int H, int C>
+__global__ __launch_bounds__(256) void agg_bwd_dst_generic_kernel(
+    const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
+    const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
+    const float *__restrict__ dout, float ns, float *__restrict__ row_stats) {
+  const int i = row_begin + xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_in_block();
+  if (i >= row_end) return;
+  agg_bwd_dst_row<H, C>(i, rowptr, col, h, a_src, a_dst, dout, ns, row_stats);
+}
+
 // One workgroup per 4 rows (a persistent grid of 2-3 workgroups per CU, leaving slots to the side
 // stream's GEMMs, measured the same step or slower and was removed).
 // REMAP: the XCD-aware block order (each XCD a contiguous row range: the rows of a banded Hi-C
 // neighbourhood share that XCD's L2).  Off (plain round-robin over the XCDs) for the multi-GPU "slab"
 // pass, whose heavy rows -- the rank's own diagonal block -- are contiguous: under the remap they
 // would all land on one XCD.
-template <bool SPLIT = false, bool REMAP = true>
+// MK is empty or one AttnMaskArgs: attention dropout (DROP; gat_agg.hpp) is the same kernel with the
+// mask arguments appended, as in the forward (gat_fwd.hip); no SPLIT form.
+template <bool SPLIT = false, bool REMAP = true, class... MK>
 __global__ __launch_bounds__(256) void agg_bwd_src_h2c256_kernel(
     const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
     const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
     const float *__restrict__ row_stats, int64_t ldr, const float *__restrict__ dout, int64_t ldq,
     const float *__restrict__ att_s, const float *__restrict__ att_d, float ns,
-    float *__restrict__ dh, float *__restrict__ da_src) {
+    float *__restrict__ dh, float *__restrict__ da_src, MK... mk) {
   const int r = row_begin + (REMAP ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x) * 4 + wave_in_block();
   if (r < row_end)
-    agg_bwd_src_row<2, 256, SPLIT>(r, rowptr, col, h, a_src, a_dst, row_stats, ldr, dout, ldq, att_s, att_d, ns, dh,
-                                   da_src);
+    agg_bwd_src_row<2, 256, SPLIT, sizeof...(MK) != 0>(r, rowptr, col, h, a_src, a_dst, row_stats, ldr, dout, ldq,
+                                                       att_s, att_d, ns, dh, da_src, mk...);
 }
 
-// The source pass with attention dropout (DROP; gat_agg.hpp): a kernel of its own, so that the one
-// above keeps its arguments and code.  No SPLIT form, and no occupancy cap: nobody has measured one.
-template <bool REMAP>
-__global__ __launch_bounds__(256) void agg_bwd_src_drop_h2c256_kernel(
+template <int H, int C, bool REMAP, class... MK>
+__global__ __launch_bounds__(256) void agg_bwd_src_generic_kernel(
     const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
     const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
     const float *__restrict__ row_stats, int64_t ldr, const float *__restrict__ dout, int64_t ldq,
     const float *__restrict__ att_s, const float *__restrict__ att_d, float ns,
-    float *__restrict__ dh, float *__restrict__ da_src, AttnMaskArgs mk) {
+    float *__restrict__ dh, float *__restrict__ da_src, MK... mk) {
   const int r = row_begin + (REMAP ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x) * 4 + wave_in_block();
-  if (r < row_end)
-    agg_bwd_src_row<2, 256, false, true>(r, rowptr, col, h, a_src, a_dst, row_stats, ldr, dout, ldq, att_s, att_d, ns,
-                                         dh, da_src, mk);
+  if (r >= row_end) return;
+  agg_bwd_src_row<H, C, false, sizeof...(MK) != 0>(r, rowptr, col, h, a_src, a_dst, row_stats, ldr, dout, ldq, att_s,
+                                                   att_d, ns, dh, da_src, mk...);
 }
 
 template <int ACT>
@@ -80,6 +91,19 @@ __global__ __launch_bounds__(256) void agg_bwd_rows_kernel(int row_begin, int ro
                                                            float *__restrict__ row_stats) {
   const int i = row_begin + blockIdx.x * 4 + wave_in_block();
   if (i < row_end) agg_bwd_rows_row<2, 256, ACT>(i, g, y, bias, out2, dout, ldq, row_stats);
+}
+
+template <int H, int C, int ACT>
+__global__ __launch_bounds__(256) void agg_bwd_rows_generic_kernel(int row_begin, int row_end,
+                                                                   const float *__restrict__ g,
+                                                                   const float *__restrict__ y,
+                                                                   const float *__restrict__ bias,
+                                                                   const float *__restrict__ out2,
+                                                                   float *__restrict__ dout, int64_t ldq,
+                                                                   float *__restrict__ row_stats) {
+  const int i = row_begin + blockIdx.x * 4 + wave_in_block();
+  if (i >= row_end) return;
+  agg_bwd_rows_row<H, C, ACT>(i, g, y, bias, out2, dout, ldq, row_stats);
 }
 
 // ---- GATConv parameter gradients: deterministic two-stage column reductions over N rows. ------
@@ -167,11 +191,12 @@ __global__ __launch_bounds__(256) void param_grad_stage2(const float *__restrict
   }
 }
 
-// Unused dynamic LDS per workgroup of the whole-graph source pass (hicgat_gat_agg_bwd_src): 5
-// workgroups per CU (the 160 KiB / 32 KiB) instead of the 7 its 68 VGPRs allow -- fewer rows in
-// flight per CU (L2 misses), and the side stream's dW kernels wait for the pass instead of sharing
-// its CUs: single-GPU step -8 us alone, -20 us with the forward gather's cap (gat_fwd.hip; 3 per CU:
-// even, 6 per CU: even), profiles/r05at_gather_occupancy_ab.txt
+// Unused dynamic LDS per workgroup of the whole-graph source pass at (2, 256): 5 workgroups per CU
+// (the 160 KiB / 32 KiB) instead of the 7 its 68 VGPRs allow -- fewer rows in flight per CU (L2
+// misses), and the side stream's dW kernels wait for the pass instead of sharing its CUs: single-GPU
+// step -8 us alone, -20 us with the forward gather's cap (gat_fwd.hip; 3 per CU: even, 6 per CU:
+// even), profiles/r05at_gather_occupancy_ab.txt.  It goes with the remapped pass of that kernel only:
+// the round-robin order, the DROP form and the other shapes are unmeasured and launch without it.
 constexpr size_t kSrcOccLds = 32768;
 
 // The gather half of hicgat_gat_agg_bwd_src_tiled (gat_tiles.hip): the sparse remainder's shares.
@@ -185,24 +210,55 @@ int agg_bwd_src_split_launch(const int *rowptr_s, const int *col_s, int row_begi
   return HICGAT_OK;
 }
 
-// gat_generic.hip: the supported-shape rule and the kernels of every supported shape but (2, 256)
-// (launched without kSrcOccLds: unmeasured for those shapes)
-bool gat_shape_supported(int H, int C);
-int agg_bwd_rows_generic_launch(int H, int C, int row_begin, int row_end, int act, const float *g, const float *y,
-                                const float *bias, const float *out2, float *dout, int64_t ldq4,
-                                float *row_stats, hipStream_t s);
-int agg_bwd_dst_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
-                               const float *h, const float *a_src, const float *a_dst, const float *dout, float ns,
-                               float *row_stats, hipStream_t s);
-int agg_bwd_src_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
-                               const float *h, const float *a_src, const float *a_dst, const float *row_stats,
-                               int64_t ldr, const float *dout, int64_t ldq4, const float *att_s, const float *att_d,
-                               float ns, float *dh, float *da_src, bool remap, hipStream_t s);
-int agg_bwd_src_drop_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
-                                    const float *h, const float *a_src, const float *a_dst, const float *row_stats,
-                                    int64_t ldr, const float *dout, int64_t ldq4, const float *att_s,
-                                    const float *att_d, float ns, float *dh, float *da_src, bool remap,
-                                    const AttnMaskArgs &mk, hipStream_t s);
+// The source pass's one launch: REMAP = remap, DROP = a mask given.
+template <class... MK>
+int agg_bwd_src_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end, const float *h,
+                       const float *a_src, const float *a_dst, const float *row_stats, int64_t ldr, const float *dout,
+                       int64_t ldq4, const float *att_s, const float *att_d, float ns, float *dh, float *da_src,
+                       bool remap, hipStream_t s, MK... mk) {
+  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+  return for_gat_shape(H, C, [&](auto shape) {
+    return with_flags(
+        [&](auto rm) {
+          using S = decltype(shape);
+          constexpr bool REMAP = rm.value;
+          if constexpr (S::h2c256)
+            hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<false, REMAP, MK...>), grid, block,
+                               REMAP && !sizeof...(MK) ? kSrcOccLds : 0, s, rowptr, col, row_begin, row_end, h, a_src,
+                               a_dst, row_stats, ldr, dout, ldq4, att_s, att_d, ns, dh, da_src, mk...);
+          else
+            hipLaunchKernelGGL((agg_bwd_src_generic_kernel<S::H, S::C, REMAP, MK...>), grid, block, 0, s, rowptr, col,
+                               row_begin, row_end, h, a_src, a_dst, row_stats, ldr, dout, ldq4, att_s, att_d, ns, dh,
+                               da_src, mk...);
+          HICGAT_CHECK_LAUNCH();
+          return HICGAT_OK;
+        },
+        remap);
+  });
+}
+
+// What hicgat_gat_agg_bwd_src and hicgat_gat_agg_drop_bwd_src check and do; mk: NULL without dropout.
+// HICGAT_SRC_ROUND_ROBIN turns the XCD remap off.
+static int agg_bwd_src_checked(const int32_t *rowptr, const int32_t *col, int N, int H, int C, int row_begin,
+                               int row_end, const float *h, const float *a_src, const float *a_dst,
+                               const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
+                               const float *att_src, const float *att_dst, float neg_slope, float *dh, float *da_src,
+                               int flags, const AttnMaskArgs *mk, hipStream_t s) {
+  if (flags & ~HICGAT_SRC_ROUND_ROBIN) return HICGAT_EINVAL;
+  const bool remap = !(flags & HICGAT_SRC_ROUND_ROBIN);
+  if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
+  if (ld_stats < 4 * H || ld_stats % 4 || ld_dout < H * C || ld_dout % 4) return HICGAT_EINVAL;
+  if (row_end == row_begin) return HICGAT_OK;
+  if (!rowptr || !col || !h || !a_src || !a_dst || !row_stats || !dout || !att_src || !att_dst ||
+      !dh || !da_src)
+    return HICGAT_EINVAL;
+  if (mk)
+    return agg_bwd_src_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
+                              ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, remap, s, *mk);
+  return agg_bwd_src_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
+                            ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, remap, s);
+}
 
 }  // namespace hicgat
 
@@ -216,19 +272,21 @@ extern "C" int hicgat_gat_agg_bwd_dst(const int32_t *rowptr, const int32_t *col,
   if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
   if (row_end == row_begin) return HICGAT_OK;
   if (!rowptr || !col || !h || !a_src || !a_dst || !dout || !row_stats) return HICGAT_EINVAL;
-  if (H != 2 || C != 256)
-    return agg_bwd_dst_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, dout, neg_slope,
-                                      row_stats, (hipStream_t)stream);
-  const int rows = row_end - row_begin;
-  hipLaunchKernelGGL(agg_bwd_dst_h2c256_kernel, dim3((rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, rowptr, col, row_begin, row_end, h, a_src, a_dst, dout,
-                     neg_slope, row_stats);
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
+  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  return for_gat_shape(H, C, [&](auto shape) {
+    using S = decltype(shape);
+    if constexpr (S::h2c256)
+      hipLaunchKernelGGL(agg_bwd_dst_h2c256_kernel, grid, block, 0, s, rowptr, col, row_begin, row_end, h, a_src, a_dst,
+                         dout, neg_slope, row_stats);
+    else
+      hipLaunchKernelGGL((agg_bwd_dst_generic_kernel<S::H, S::C>), grid, block, 0, s, rowptr, col, row_begin, row_end,
+                         h, a_src, a_dst, dout, neg_slope, row_stats);
+    HICGAT_CHECK_LAUNCH();
+    return HICGAT_OK;
+  });
 }
 
-// HICGAT_SRC_ROUND_ROBIN turns the XCD remap off; the occupancy cap goes with the remapped
-// (whole-graph) pass at (2, 256) only.
 extern "C" int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H,
                                       int C, int row_begin, int row_end, const float *h,
                                       const float *a_src, const float *a_dst,
@@ -236,30 +294,8 @@ extern "C" int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col,
                                       int64_t ld_dout, const float *att_src, const float *att_dst,
                                       float neg_slope, float *dh, float *da_src, int flags,
                                       hicgat_stream_t stream) {
-  if (flags & ~HICGAT_SRC_ROUND_ROBIN) return HICGAT_EINVAL;
-  const bool remap = !(flags & HICGAT_SRC_ROUND_ROBIN);
-  if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
-  if (ld_stats < 4 * H || ld_stats % 4 || ld_dout < H * C || ld_dout % 4) return HICGAT_EINVAL;
-  if (row_end == row_begin) return HICGAT_OK;
-  if (!rowptr || !col || !h || !a_src || !a_dst || !row_stats || !dout || !att_src || !att_dst ||
-      !dh || !da_src)
-    return HICGAT_EINVAL;
-  if (H != 2 || C != 256)
-    return agg_bwd_src_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats,
-                                      dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, remap,
-                                      (hipStream_t)stream);
-  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
-  if (remap)
-    hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<false, true>), grid, block, kSrcOccLds, (hipStream_t)stream,
-                       rowptr, col, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout, ld_dout / 4,
-                       att_src, att_dst, neg_slope, dh, da_src);
-  else
-    hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<false, false>), grid, block, 0, (hipStream_t)stream, rowptr, col,
-                       row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout, ld_dout / 4, att_src,
-                       att_dst, neg_slope, dh, da_src);
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
+  return agg_bwd_src_checked(rowptr, col, N, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
+                             ld_dout, att_src, att_dst, neg_slope, dh, da_src, flags, nullptr, (hipStream_t)stream);
 }
 
 // ---- attention dropout: hicgat_gat_agg_bwd_src with the forward's keep factors recomputed ---------
@@ -270,32 +306,10 @@ extern "C" int hicgat_gat_agg_drop_bwd_src(const int32_t *rowptr, const int32_t 
                                            const float *att_dst, float neg_slope, float *dh, float *da_src,
                                            int flags, double p, uint64_t seed, const int64_t *step_counter,
                                            int64_t step_value, uint32_t site, hicgat_stream_t stream) {
-  if (flags & ~HICGAT_SRC_ROUND_ROBIN) return HICGAT_EINVAL;
-  const bool remap = !(flags & HICGAT_SRC_ROUND_ROBIN);
-  if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
   if (!p_ok(p) || !attn_site_ok(site) || misaligned(step_counter, 8)) return HICGAT_EINVAL;
-  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
-  if (ld_stats < 4 * H || ld_stats % 4 || ld_dout < H * C || ld_dout % 4) return HICGAT_EINVAL;
-  if (row_end == row_begin) return HICGAT_OK;
-  if (!rowptr || !col || !h || !a_src || !a_dst || !row_stats || !dout || !att_src || !att_dst ||
-      !dh || !da_src)
-    return HICGAT_EINVAL;
   const AttnMaskArgs mk = attn_mask_args(p, seed, step_counter, step_value, site);
-  hipStream_t s = (hipStream_t)stream;
-  if (H != 2 || C != 256)
-    return agg_bwd_src_drop_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats,
-                                           dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, remap, mk, s);
-  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
-  if (remap)
-    hipLaunchKernelGGL((agg_bwd_src_drop_h2c256_kernel<true>), grid, block, 0, s, rowptr, col, row_begin, row_end, h,
-                       a_src, a_dst, row_stats, ld_stats, dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src,
-                       mk);
-  else
-    hipLaunchKernelGGL((agg_bwd_src_drop_h2c256_kernel<false>), grid, block, 0, s, rowptr, col, row_begin, row_end, h,
-                       a_src, a_dst, row_stats, ld_stats, dout, ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src,
-                       mk);
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
+  return agg_bwd_src_checked(rowptr, col, N, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
+                             ld_dout, att_src, att_dst, neg_slope, dh, da_src, flags, &mk, (hipStream_t)stream);
 }
 
 extern "C" int hicgat_gat_agg_bwd_rows(int N, int H, int C, int row_begin, int row_end, int act,
@@ -308,18 +322,25 @@ extern "C" int hicgat_gat_agg_bwd_rows(int N, int H, int C, int row_begin, int r
   if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
   if (row_end == row_begin) return HICGAT_OK;
   if (!g || !y || !bias || !out2 || !row_stats || (act && !dout)) return HICGAT_EINVAL;
-  if (H != 2 || C != 256)
-    return agg_bwd_rows_generic_launch(H, C, row_begin, row_end, act, g, y, bias, out2, dout, ld_dout / 4, row_stats,
-                                       (hipStream_t)stream);
-  const int rows = row_end - row_begin;
-  if (act)
-    hipLaunchKernelGGL(agg_bwd_rows_kernel<1>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       row_begin, row_end, g, y, bias, out2, dout, ld_dout / 4, row_stats);
-  else
-    hipLaunchKernelGGL(agg_bwd_rows_kernel<0>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       row_begin, row_end, g, y, bias, out2, dout, (int64_t)0, row_stats);
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
+  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t ldq4 = act ? ld_dout / 4 : 0;   // act = 0 writes no dout
+  return for_gat_shape(H, C, [&](auto shape) {
+    return with_flags(
+        [&](auto relu) {
+          using S = decltype(shape);
+          constexpr int ACT = relu.value;
+          if constexpr (S::h2c256)
+            hipLaunchKernelGGL(agg_bwd_rows_kernel<ACT>, grid, block, 0, s, row_begin, row_end, g, y, bias, out2, dout,
+                               ldq4, row_stats);
+          else
+            hipLaunchKernelGGL((agg_bwd_rows_generic_kernel<S::H, S::C, ACT>), grid, block, 0, s, row_begin, row_end, g,
+                               y, bias, out2, dout, ldq4, row_stats);
+          HICGAT_CHECK_LAUNCH();
+          return HICGAT_OK;
+        },
+        act != 0);
+  });
 }
 
 extern "C" size_t hicgat_gat_param_grad_workspace_bytes(int N, int D) {
@@ -348,15 +369,11 @@ extern "C" int hicgat_gat_param_grad(const float *h, const float *dout, const fl
   if (dbias) out.o[P++] = dbias;
   hipStream_t s = (hipStream_t)stream;
   if (nblk > 0) {
-#define HICGAT_PG1(PARTS_)                                                                                      \
-  case PARTS_:                                                                                                  \
-    hipLaunchKernelGGL(param_grad_stage1<PARTS_>, dim3(nblk), dim3(128), 0, s, h, dout, da_src, row_stats, N, H, \
-                       C, rpb, part);                                                                           \
-    break;
-    switch (parts) {
-      HICGAT_PG1(1) HICGAT_PG1(2) HICGAT_PG1(3) HICGAT_PG1(4) HICGAT_PG1(5) HICGAT_PG1(6) HICGAT_PG1(7)
-    }
-#undef HICGAT_PG1
+    static constexpr decltype(&param_grad_stage1<1>) kStage1[8] = {   // by PARTS (1..7)
+        nullptr,
+        param_grad_stage1<1>, param_grad_stage1<2>, param_grad_stage1<3>, param_grad_stage1<4>,
+        param_grad_stage1<5>, param_grad_stage1<6>, param_grad_stage1<7>};
+    hipLaunchKernelGGL(kStage1[parts], dim3(nblk), dim3(128), 0, s, h, dout, da_src, row_stats, N, H, C, rpb, part);
     HICGAT_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(param_grad_stage2, dim3((P * D + kPG2Cols - 1) / kPG2Cols), dim3(kPG2Cols * kPG2Groups), 0, s,

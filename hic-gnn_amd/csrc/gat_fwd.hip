@@ -1,9 +1,11 @@
-// GATConv forward on gfx950: attention logits (a2) and the entry points of the fused edge-softmax +
-// aggregation (a4+a5), whose per-row body is agg_fwd_row (gat_agg.hpp: reference ops, layout, design).
-// Here: the logits kernel, the (2, 256) entry kernel with its measured launch parameters, and the C
-// ABI, which routes every other supported shape to gat_generic.hip.  A launch covers rows
+// GATConv forward on gfx950: attention logits (a2) and the fused edge-softmax + aggregation (a4+a5),
+// whose per-row body is agg_fwd_row (gat_agg.hpp: reference ops, layout, design).  Here: the logits
+// kernel, the entry kernels of the aggregation -- one for (2, 256) with its measured launch
+// parameters, one for every other supported shape -- their one launch (the dispatcher is
+// gat_launch.hpp's), the attention-dropout mask kernel, and the C ABI.  A launch covers rows
 // [row_begin, row_end) (a rank's destination shard).
 #include "gat_agg.hpp"
+#include "gat_launch.hpp"
 
 namespace hicgat {
 
@@ -42,17 +44,42 @@ __global__ __launch_bounds__(256) void att_logits_kernel(const float *__restrict
 // at <2, 256> (lane l holds float4 #l of head 0 and float4 #l of head 1, 8 neighbours in flight)
 // under the name the profiles and bench.py know, with its own launch bounds.  SPLIT is the gather
 // half of the tiled form (gat_tiles.hip).
-template <bool TRAIN, int ACT, bool SPLIT = false>
+// MK is empty or one AttnMaskArgs: attention dropout (DROP; gat_agg.hpp) is the same kernel with the
+// mask arguments appended.  With the empty pack the arguments and the body are those of a kernel
+// that knows no dropout, so those instances' code does not depend on DROP existing.
+template <bool TRAIN, int ACT, bool SPLIT = false, class... MK>
 __global__ __launch_bounds__(256, 1) void agg_fwd_h2c256_kernel(
     const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
     const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
     const float *__restrict__ bias, float ns, float *__restrict__ out, float *__restrict__ out2,
     float *__restrict__ row_stats, const int *__restrict__ rowptr_s = nullptr,
-    const int *__restrict__ col_s = nullptr) {
+    const int *__restrict__ col_s = nullptr, MK... mk) {
   const int i = row_begin + xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_in_block();
   if (i < row_end)
-    agg_fwd_row<2, 256, TRAIN, ACT, SPLIT>(i, rowptr, col, rowptr_s, col_s, h, a_src, a_dst, bias, ns, out, out2,
-                                           row_stats);
+    agg_fwd_row<2, 256, TRAIN, ACT, SPLIT, sizeof...(MK) != 0>(i, rowptr, col, rowptr_s, col_s, h, a_src, a_dst, bias,
+                                                               ns, out, out2, row_stats, mk...);
+}
+
+// Every other supported shape (the ones the reference's model zoo instantiates, models.py:
+// GATConv(512, 128, heads=2), (512, 512, heads=2), (256, 256, heads=4), (512, 512, heads=1), ...).
+template <int H, int C, bool TRAIN, int ACT, class... MK>
+__global__ __launch_bounds__(256) void agg_fwd_generic_kernel(
+    const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
+    const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
+    const float *__restrict__ bias, float ns, float *__restrict__ out, float *__restrict__ out2,
+    float *__restrict__ row_stats, MK... mk) {
+  const int i = row_begin + xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_in_block();
+  if (i >= row_end) return;
+  agg_fwd_row<H, C, TRAIN, ACT, false, sizeof...(MK) != 0>(i, rowptr, col, nullptr, nullptr, h, a_src, a_dst, bias,
+                                                           ns, out, out2, row_stats, mk...);
+}
+
+template <int H>
+__global__ __launch_bounds__(256) void attn_mask_kernel(const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                        int N, AttnMaskArgs mk, uint8_t *__restrict__ mask) {
+  const int i = blockIdx.x * 4 + wave_in_block();
+  if (i >= N) return;
+  attn_mask_row<H>(i, rowptr, col, mk, mask);
 }
 
 // The gather half of hicgat_gat_agg_fwd_tiled (gat_tiles.hip): raw sums over the sparse remainder.
@@ -60,41 +87,65 @@ int agg_fwd_split_launch(const int *rowptr, const int *col, const int *rowptr_s,
                          int row_end, const float *h, const float *a_src, const float *a_dst, float ns, float *out,
                          float *out2, float *row_stats, hipStream_t s) {
   const dim3 grid((row_end - row_begin + 3) / 4), block(256);
-  if (out2)
-    hipLaunchKernelGGL((agg_fwd_h2c256_kernel<true, 0, true>), grid, block, 0, s, rowptr, col, row_begin, row_end,
-                       h, a_src, a_dst, nullptr, ns, out, out2, row_stats, rowptr_s, col_s);
-  else
-    hipLaunchKernelGGL((agg_fwd_h2c256_kernel<false, 0, true>), grid, block, 0, s, rowptr, col, row_begin, row_end,
-                       h, a_src, a_dst, nullptr, ns, out, out2, row_stats, rowptr_s, col_s);
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
+  return with_flags(
+      [&](auto train) {
+        hipLaunchKernelGGL((agg_fwd_h2c256_kernel<train.value, 0, true>), grid, block, 0, s, rowptr, col, row_begin,
+                           row_end, h, a_src, a_dst, nullptr, ns, out, out2, row_stats, rowptr_s, col_s);
+        HICGAT_CHECK_LAUNCH();
+        return HICGAT_OK;
+      },
+      out2 != nullptr);
 }
 
-// The same row body with attention dropout (DROP; gat_agg.hpp): a kernel of its own, so that the one
-// above keeps its arguments and code.  No SPLIT form, and no occupancy cap: nobody has measured one.
-template <bool TRAIN, int ACT>
-__global__ __launch_bounds__(256, 1) void agg_fwd_drop_h2c256_kernel(
-    const int *__restrict__ rowptr, const int *__restrict__ col, int row_begin, int row_end,
-    const float *__restrict__ h, const float *__restrict__ a_src, const float *__restrict__ a_dst,
-    const float *__restrict__ bias, float ns, float *__restrict__ out, float *__restrict__ out2,
-    float *__restrict__ row_stats, AttnMaskArgs mk) {
-  const int i = row_begin + xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_in_block();
-  if (i < row_end)
-    agg_fwd_row<2, 256, TRAIN, ACT, false, true>(i, rowptr, col, nullptr, nullptr, h, a_src, a_dst, bias, ns, out,
-                                                 out2, row_stats, mk);
+// Unused dynamic LDS per workgroup of the (2, 256) gather launch: 3 workgroups per CU (160 KiB / 52 KiB)
+// instead of the 4 its 98 VGPRs allow -- fewer rows in flight per CU, fewer L2 misses: the
+// single-GPU step 1.798-1.803 vs 1.820-1.821 ms together with the source pass's cap (gat_bwd.hip;
+// 2 per CU: +30 us), profiles/r05at_gather_occupancy_ab.txt.  Measured for that kernel at N = 20000
+// only: the DROP form and the other shapes launch without it.
+constexpr size_t kAggFwdOccLds = 53248;
+
+// The forward's one launch: TRAIN = out2 given, ACT = act, DROP = a mask given.
+template <class... MK>
+int agg_fwd_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end, const float *h,
+                   const float *a_src, const float *a_dst, const float *bias, float ns, int act, float *out,
+                   float *out2, float *row_stats, hipStream_t s, MK... mk) {
+  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+  return for_gat_shape(H, C, [&](auto shape) {
+    return with_flags(
+        [&](auto train, auto relu) {
+          using S = decltype(shape);
+          constexpr bool TRAIN = train.value;
+          constexpr int ACT = relu.value;
+          if constexpr (S::h2c256)
+            hipLaunchKernelGGL((agg_fwd_h2c256_kernel<TRAIN, ACT, false, MK...>), grid, block,
+                               sizeof...(MK) ? 0 : kAggFwdOccLds, s, rowptr, col, row_begin, row_end, h, a_src, a_dst,
+                               bias, ns, out, out2, row_stats, nullptr, nullptr, mk...);
+          else
+            hipLaunchKernelGGL((agg_fwd_generic_kernel<S::H, S::C, TRAIN, ACT, MK...>), grid, block, 0, s, rowptr,
+                               col, row_begin, row_end, h, a_src, a_dst, bias, ns, out, out2, row_stats, mk...);
+          HICGAT_CHECK_LAUNCH();
+          return HICGAT_OK;
+        },
+        out2 != nullptr, act != 0);
+  });
 }
 
-// gat_generic.hip: the supported-shape rule and the kernels of every supported shape but (2, 256)
-int agg_fwd_drop_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
-                                const float *h, const float *a_src, const float *a_dst, const float *bias, float ns,
-                                int act, float *out, float *out2, float *row_stats, const AttnMaskArgs &mk,
-                                hipStream_t s);
-int attn_mask_launch(const int *rowptr, const int *col, int N, int H, const AttnMaskArgs &mk, uint8_t *mask,
-                     hipStream_t s);
-bool gat_shape_supported(int H, int C);
-int agg_fwd_generic_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end,
-                           const float *h, const float *a_src, const float *a_dst, const float *bias, float ns,
-                           int act, float *out, float *out2, float *row_stats, hipStream_t s);
+// What hicgat_gat_agg_fwd and hicgat_gat_agg_drop_fwd check and do; mk: NULL without dropout.
+static int agg_fwd_checked(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C, int row_begin,
+                    int row_end, const float *h, const float *a_src, const float *a_dst, const float *bias,
+                    float neg_slope, int act, float *out, float *out2, float *row_stats, const AttnMaskArgs *mk,
+                    hipStream_t s) {
+  if (N < 0 || nnz < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
+  if (act != 0 && act != 1) return HICGAT_EINVAL;
+  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
+  if (row_end == row_begin) return HICGAT_OK;
+  if (!rowptr || !col || !h || !a_src || !a_dst || !bias || !out || !row_stats) return HICGAT_EINVAL;
+  if (mk)
+    return agg_fwd_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out, out2,
+                          row_stats, s, *mk);
+  return agg_fwd_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out, out2,
+                        row_stats, s);
+}
 
 }  // namespace hicgat
 
@@ -112,41 +163,13 @@ extern "C" int hicgat_gat_att_logits(const float *h, const float *att_src, const
   return HICGAT_OK;
 }
 
-// Unused dynamic LDS per workgroup of the gather launch below: 3 workgroups per CU (160 KiB / 52 KiB)
-// instead of the 4 its 98 VGPRs allow -- fewer rows in flight per CU, fewer L2 misses: the
-// single-GPU step 1.798-1.803 vs 1.820-1.821 ms together with the source pass's cap (gat_bwd.hip;
-// 2 per CU: +30 us), profiles/r05at_gather_occupancy_ab.txt
-constexpr size_t kAggFwdOccLds = 53248;
-
 extern "C" int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz,
                                   int H, int C, int row_begin, int row_end, const float *h,
                                   const float *a_src, const float *a_dst, const float *bias,
                                   float neg_slope, int act, float *out, float *out2,
                                   float *row_stats, hicgat_stream_t stream) {
-  if (N < 0 || nnz < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (act != 0 && act != 1) return HICGAT_EINVAL;
-  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
-  if (row_end == row_begin) return HICGAT_OK;
-  if (!rowptr || !col || !h || !a_src || !a_dst || !bias || !out || !row_stats) return HICGAT_EINVAL;
-  if (H != 2 || C != 256)   // the generic kernels, without the (2, 256) launch's occupancy cap (unmeasured there)
-    return agg_fwd_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out,
-                                  out2, row_stats, (hipStream_t)stream);
-  const int rows = row_end - row_begin;
-  const dim3 grid((rows + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define HICGAT_FWD_LAUNCH(TR, AC)                                                                  \
-  hipLaunchKernelGGL((agg_fwd_h2c256_kernel<TR, AC>), grid, block, kAggFwdOccLds, s, rowptr, col, row_begin, \
-                     row_end, h, a_src, a_dst, bias, neg_slope, out, out2, row_stats)
-  if (out2) {
-    if (act) HICGAT_FWD_LAUNCH(true, 1);
-    else HICGAT_FWD_LAUNCH(true, 0);
-  } else {
-    if (act) HICGAT_FWD_LAUNCH(false, 1);
-    else HICGAT_FWD_LAUNCH(false, 0);
-  }
-#undef HICGAT_FWD_LAUNCH
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
+  return agg_fwd_checked(rowptr, col, N, nnz, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out,
+                         out2, row_stats, nullptr, (hipStream_t)stream);
 }
 
 // ---- attention dropout: hicgat_gat_agg_fwd with each alpha_ij multiplied by its keep factor ------
@@ -156,31 +179,10 @@ extern "C" int hicgat_gat_agg_drop_fwd(const int32_t *rowptr, const int32_t *col
                                        float *out2, float *row_stats, double p, uint64_t seed,
                                        const int64_t *step_counter, int64_t step_value, uint32_t site,
                                        hicgat_stream_t stream) {
-  if (N < 0 || nnz < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (act != 0 && act != 1) return HICGAT_EINVAL;
   if (!p_ok(p) || !attn_site_ok(site) || misaligned(step_counter, 8)) return HICGAT_EINVAL;
-  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
-  if (row_end == row_begin) return HICGAT_OK;
-  if (!rowptr || !col || !h || !a_src || !a_dst || !bias || !out || !row_stats) return HICGAT_EINVAL;
   const AttnMaskArgs mk = attn_mask_args(p, seed, step_counter, step_value, site);
-  hipStream_t s = (hipStream_t)stream;
-  if (H != 2 || C != 256)
-    return agg_fwd_drop_generic_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act,
-                                       out, out2, row_stats, mk, s);
-  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
-#define HICGAT_FWD_LAUNCH(TR, AC)                                                                             \
-  hipLaunchKernelGGL((agg_fwd_drop_h2c256_kernel<TR, AC>), grid, block, 0, s, rowptr, col, row_begin, row_end, \
-                     h, a_src, a_dst, bias, neg_slope, out, out2, row_stats, mk)
-  if (out2) {
-    if (act) HICGAT_FWD_LAUNCH(true, 1);
-    else HICGAT_FWD_LAUNCH(true, 0);
-  } else {
-    if (act) HICGAT_FWD_LAUNCH(false, 1);
-    else HICGAT_FWD_LAUNCH(false, 0);
-  }
-#undef HICGAT_FWD_LAUNCH
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
+  return agg_fwd_checked(rowptr, col, N, nnz, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out,
+                         out2, row_stats, &mk, (hipStream_t)stream);
 }
 
 extern "C" int hicgat_gat_attn_mask(const int32_t *rowptr, const int32_t *col, int N, int H, double p, uint64_t seed,
@@ -190,6 +192,15 @@ extern "C" int hicgat_gat_attn_mask(const int32_t *rowptr, const int32_t *col, i
   if (H < 1 || H > 4) return HICGAT_EUNSUPPORTED;
   if (N == 0) return HICGAT_OK;
   if (!rowptr || !col || !mask) return HICGAT_EINVAL;
-  return attn_mask_launch(rowptr, col, N, H, attn_mask_args(p, seed, step_counter, step_value, site), mask,
-                          (hipStream_t)stream);
+  const AttnMaskArgs mk = attn_mask_args(p, seed, step_counter, step_value, site);
+  const dim3 grid((N + 3) / 4), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  switch (H) {
+    case 1: hipLaunchKernelGGL(attn_mask_kernel<1>, grid, block, 0, s, rowptr, col, N, mk, mask); break;
+    case 2: hipLaunchKernelGGL(attn_mask_kernel<2>, grid, block, 0, s, rowptr, col, N, mk, mask); break;
+    case 3: hipLaunchKernelGGL(attn_mask_kernel<3>, grid, block, 0, s, rowptr, col, N, mk, mask); break;
+    default: hipLaunchKernelGGL(attn_mask_kernel<4>, grid, block, 0, s, rowptr, col, N, mk, mask); break;
+  }
+  HICGAT_CHECK_LAUNCH();
+  return HICGAT_OK;
 }

@@ -26,18 +26,11 @@
 // at columns 128w + 4n .. 4n+3 of neighbour k of a k-pair, and component t feeds the MFMA of output
 // chunk t -- so chunk t's column n is feature 128w + 4n + t and the epilogue stores float4s.
 #include "common.hpp"
+#include "gat_launch.hpp"   // the SPLIT gather launches of gat_fwd.hip / gat_bwd.hip
 
 namespace hicgat {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-int agg_fwd_split_launch(const int *rowptr, const int *col, const int *rowptr_s, const int *col_s, int row_begin,
-                         int row_end, const float *h, const float *a_src, const float *a_dst, float ns, float *out,
-                         float *out2, float *row_stats, hipStream_t s);   // gat_fwd.hip
-int agg_bwd_src_split_launch(const int *rowptr_s, const int *col_s, int row_begin, int row_end, const float *h,
-                             const float *a_src, const float *a_dst, const float *row_stats, int64_t ldr,
-                             const float *dout, int64_t ldq4, float ns, float *dh, float *da_src,
-                             hipStream_t s);   // gat_bwd.hip
 
 __device__ __forceinline__ float f4_c(const float4 &v, int t) { return t == 0 ? v.x : t == 1 ? v.y : t == 2 ? v.z : v.w; }
 

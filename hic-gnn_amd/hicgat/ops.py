@@ -1053,7 +1053,7 @@ ATTN_SITE_LIMIT = 1 << 31   # include/hicgat.h HICGAT_ATTN_SITE_BIT: attention-d
 
 def gat_shape_supported(H, C):
     """Whether the aggregation kernels run GATConv(heads=H, out_channels=C) (include/hicgat.h; the
-    rule of gat_generic.hip, usable without the library loaded)."""
+    rule of gat_launch.hpp, usable without the library loaded)."""
     H, C = int(H), int(C)
     return 1 <= H <= 4 and C > 0 and C % 128 == 0 and (H * C) % 256 == 0 and H * C <= 1024
 

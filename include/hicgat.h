@@ -85,7 +85,7 @@ int hicgat_gat_att_logits(const float *h, const float *att_src, const float *att
  * (every GATConv of models.py: (H, C) = (1, 256), (1, 512), (2, 128), (2, 256), (2, 512), (4, 256), ...);
  * other shapes return HICGAT_EUNSUPPORTED.  H == 2, C == 256 (the flagship's GATConv(512, 256,
  * heads=2), models.py:619) has entry kernels and launch parameters of its own around the per-row bodies
- * that every shape shares (gat_agg.hpp); the rest are launched from gat_generic.hip.
+ * that every shape shares (gat_agg.hpp); one dispatcher (gat_launch.hpp) launches both kinds.
  * The same set holds for hicgat_gat_agg_bwd_dst, hicgat_gat_agg_bwd_rows and hicgat_gat_agg_bwd_src;
  * the tiled (hicgat_gat_agg_*_tiled) and aggregate-first (hicgat_xagg_*) forms stay H == 2, C == 256.
  * nnz = rowptr[N] (checked >= 0 only).  bias [H*C].  act = 1 writes out = relu(sum + bias) (the relu

@@ -1,6 +1,6 @@
 """GPU parity of ``hicgat.GATConv`` at every (in, out, heads) the reference's models.py instantiates,
-against ``oracle.gat.GATConv`` -- the generic aggregation kernels (gat_generic.hip) and the routing
-around them (ops.gat_conv, the fused tail, the two zoo models).
+against ``oracle.gat.GATConv`` -- the generic aggregation kernels (gat_fwd.hip, gat_bwd.hip; the shape
+list of gat_launch.hpp) and the routing around them (ops.gat_conv, the fused tail, the two zoo models).
 
 Tolerances are those of tests/test_gpu_parity.py: outputs rtol 1e-5 / atol 1e-6, gradients 1e-4
 relative to the tensor's max magnitude; the long-row test's atol 2e-6; the rows-pass test's 2e-5;

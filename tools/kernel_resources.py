@@ -25,6 +25,6 @@ for f in srcs:
             info[cur][k.strip()] = v.strip()
     for k, v in info.items():
         name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip().split("(")[0]
-        print(f"{name[:60]:60s} vgpr {v.get('VGPRs','?'):>4} agpr {v.get('AGPRs','?'):>3} "
+        print(f"{name:60s} vgpr {v.get('VGPRs','?'):>4} agpr {v.get('AGPRs','?'):>3} "
               f"occ {v.get('Occupancy [waves/SIMD]','?'):>2} lds {v.get('LDS Size [bytes/block]','?'):>6} "
               f"spill {v.get('VGPRs Spill','?')}/{v.get('SGPRs Spill','?')}")
