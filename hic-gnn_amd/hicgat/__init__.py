@@ -31,6 +31,8 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
   hicgat.kr.KRnorm                            ~ r_utils.R:1-93 (normalize.R)
   hicgat.align.domain_alignment / generalize  ~ utils.py:83-109, HiC_GAT_generalize_directly.py:312-336
   hicgat.embed.node2vec                       ~ Node2Vec(...).fit(...) at HiC_GAT_generalize_directly.py:150-155
+  hicgat.embed.line                           ~ LINE(G, embedding_size=512, order='second').train(bs, ep) at
+                                                HiC-GNN_main.py:91-96 (second order only)
 Compute runs in libhicgat.so (include/hicgat.h); there is no CPU fallback.
 """
 from . import (_lib, align, dist, dropout, embed, graph, graphs, io, kernels, kr, metrics, nn, ops, optim,  # noqa: F401

@@ -146,6 +146,12 @@ SIGNATURES = {
     "hicgat_n2v_walks": (c_int, [c_p, c_p, c_p, c_int, c_p, c_int, c_int, c_f, c_f, c_u64, c_p, c_p]),
     "hicgat_n2v_sgns_epoch": (c_int, [c_p, c_int, c_int, c_p, c_p, c_int, c_int, c_int, c_int, c_f, c_f, c_int,
                                       c_int, c_u64, c_int, c_p, c_p, c_p]),
+    "hicgat_line_workspace_bytes": (c_sz, [c_int, c_int]),
+    "hicgat_line_samples": (c_int, [c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_i64, c_i64, c_int, c_int,
+                                    c_u64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+    "hicgat_line_train": (c_int, [c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_i64, c_i64, c_int, c_int, c_int,
+                                  c_u64, c_i64, c_i64, c_d, c_d, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                  c_p]),
     "hicgat_adam_step": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_d, c_i64, c_p]),
     "hicgat_adam_step_table": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_p, c_i64, c_p, c_int, c_p]),
     "hicgat_step_begin": (c_int, [c_p, c_i64, c_p, c_p]),

@@ -156,7 +156,10 @@ def make_parser():
     p.add_argument("matrix", help="Hi-C list (bin_i bin_j count) or dense matrix text file")
     p.add_argument("features", help="N x F embedding text file (np.loadtxt), or 'node2vec' to generate the "
                                     "embeddings on the GPU from the zero-diagonal contact matrix (hicgat.embed, "
-                                    "the HiC_GAT_generalize_directly.py:150-155 call)")
+                                    "the HiC_GAT_generalize_directly.py:150-155 call), or 'line' for the LINE "
+                                    "embeddings HiC-GNN_main.py:91-96 makes itself (hicgat.embed.line; -bs / -ep)")
+    p.add_argument("-bs", "--batchsize", type=int, default=128, help="LINE batch size (HiC-GNN_main.py:34)")
+    p.add_argument("-ep", "--epochs", type=int, default=10, help="LINE epochs (HiC-GNN_main.py:35)")
     p.add_argument("-c", "--conversions", default="[.1,.1,2]", help="conversion list, '[a, step, b]' or '[f]' "
                                                                     "(HiC-GNN_main.py:33)")
     p.add_argument("-lr", "--learningrate", type=float, default=1e-3)
@@ -194,6 +197,10 @@ def main(argv=None):
     if a.features == "node2vec":                # node2vec on the zero-diagonal contact graph (:150-155)
         from .embed import node2vec
         feats = node2vec(mat, seed=a.seed if a.seed else 42).cpu().numpy()
+    elif a.features == "line":                  # HiC-GNN_main.py:91-96: LINE(G, 512, order='second').train(bs, ep)
+        from . import embed
+        feats = embed.line(mat, embedding_size=512, order="second", batch_size=a.batchsize, epochs=a.epochs,
+                           seed=a.seed if a.seed else 42).cpu().numpy()
     else:
         feats = np.loadtxt(a.features).astype(np.float32)
     if not a.no_kr:                             # :85-89 (Rscript normalize.R -> r_utils.R KRnorm)

@@ -675,6 +675,61 @@ int hicgat_n2v_sgns_epoch(const int32_t *walks, int nwalks, int walk_length, con
                           float alpha1, int epoch, int epochs, uint64_t seed, int max_waves, float *syn0,
                           float *syn1, hicgat_stream_t stream);
 
+/* ---- LINE: second-order LINE embeddings, the feature generator of HiC-GNN_main.py:91-96
+ * (`LINE(G, embedding_size=512, order='second')`, `line.train(batch_size, epochs)`: the `ge` package
+ * over Keras, restated from its published source; see csrc/line.hip) ------------------------------
+ * Host-supplied tables (device pointers): the E edges (head[i], tail[i]) with their alias table
+ * (edge_accept float32, edge_alias int32) over p_edge = w / sum w; the N-entry node alias table
+ * (node_accept, node_alias) over p_node ~ deg^0.75; perm [n_pass, E]: one permutation of 0..E-1 per
+ * pass of the stream, for the passes pass_begin .. pass_begin + n_pass - 1.
+ *
+ * The sample stream.  R = 1 + negative batches per chunk, chunks = ceil(E / batch_size) chunks per
+ * pass.  Step s (a batch, counted from 0 over the whole run) lies in pass s / (chunks R), at
+ * r = s % (chunks R), chunk c = r / R, batch b = r % R; it has len = min(batch_size, E - c batch_size)
+ * samples, slot j = 0 .. len-1.  The random words of (s, j) are Philox4x32-10 as under "feature
+ * dropout" below:
+ *   counter = (j, s & 0xffffffff, s >> 32, HICGAT_LINE_SITE);  key = (seed & 0xffffffff, seed >> 32);
+ *   word -> uniform:  u(w) = (float)(w >> 8) * 2^-24        (24 bits, exact in float32, in [0, 1));
+ *   word -> index:    idx(w, n) = (uint64(w) * n) >> 32      (in [0, n)).
+ * The chunk's positives are drawn by the words of its batch 0, step s - b:
+ *   i = perm[pass][c batch_size + j];  if u(w0) >= edge_accept[i]: i = edge_alias[i];  h = head[i];
+ *   b == 0:  t = tail[i], y = +1;
+ *   b  > 0:  with the words of (s, j):  n = idx(w0, N);  t = u(w1) < node_accept[n] ? n : node_alias[n];
+ *            y = -1   (the same h as batch 0: a chunk's R batches share their heads).
+ * So (h, t, y) is a pure function of (seed, s, j) and the tables: no state passes from step to step.
+ *
+ * hicgat_line_samples writes the (h, t, y) of steps [step_begin, step_end) into h / t / y
+ * [step_end - step_begin, batch_size] int32; slots j >= len hold (-1, -1, 0).
+ *
+ * hicgat_line_train enqueues steps [step_begin, step_end), two launches each, on tables U (the
+ * embeddings, `second_emb`) and C (`context_emb`), both [N, D] fp32, with the Adam moments mU, vU,
+ * mC, vC (zero before step 0):
+ *   s_k = <U[h_k], C[t_k]>;  loss = -mean_k log sigmoid(y_k s_k);  g_k = -(y_k / len) sigmoid(-y_k s_k);
+ *   dU[h_k] += g_k C[t_k],  dC[t_k] += g_k U[h_k]   (both from the tables as they stand BEFORE the step;
+ *   duplicates summed in ascending k);  then Keras' Adam, dense over both tables, t = s + 1:
+ *   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
+ *   lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)  (host, float64);  p -= lr_t m / (sqrt(v) + eps).
+ * (Not torch's form: hicgat_adam_step divides sqrt(v) by sqrt(1-b2^t) before adding eps.)  No float
+ * atomics and one summation order: the tables after a step range are bit-reproducible.
+ * Checked before any launch: D % 64 == 0 and 64 <= D <= 1024 (else HICGAT_EUNSUPPORTED);
+ * batch_size >= 1, 0 <= negative <= 64, a step range inside the passes that perm holds, non-NULL
+ * 16-B aligned tables / moments / workspace, workspace_bytes >= hicgat_line_workspace_bytes(D,
+ * batch_size), lr >= 0, 0 <= b1, b2 < 1, eps >= 0 (else HICGAT_EINVAL).  E == 0 or an empty step range
+ * is a no-op. */
+enum { HICGAT_LINE_SITE = 0x4C494E45 };   /* "LINE": the fourth counter word of the LINE sample stream */
+size_t hicgat_line_workspace_bytes(int D, int batch_size);
+int hicgat_line_samples(const int32_t *head, const int32_t *tail, const float *edge_accept,
+                        const int32_t *edge_alias, int E, const float *node_accept, const int32_t *node_alias,
+                        int N, const int32_t *perm, int64_t pass_begin, int64_t n_pass, int batch_size,
+                        int negative, uint64_t seed, int64_t step_begin, int64_t step_end, int32_t *h,
+                        int32_t *t, int32_t *y, hicgat_stream_t stream);
+int hicgat_line_train(const int32_t *head, const int32_t *tail, const float *edge_accept,
+                      const int32_t *edge_alias, int E, const float *node_accept, const int32_t *node_alias,
+                      int N, const int32_t *perm, int64_t pass_begin, int64_t n_pass, int D, int batch_size,
+                      int negative, uint64_t seed, int64_t step_begin, int64_t step_end, double lr,
+                      double beta1, double beta2, double eps, float *U, float *C, float *mU, float *vU,
+                      float *mC, float *vC, void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
+
 /* ---- a10 (part): torch.optim.Adam step (HiC-GNN_main.py:118,130) over one flat fp32 buffer ----
  * Same arithmetic as torch's single-tensor CPU Adam (lerp / addcmul / addcdiv, no weight decay):
  *   m = fma(1-b1, g-m, m); v = fma((1-b2)*g, g, b2*v);
