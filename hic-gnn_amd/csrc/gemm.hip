@@ -15,7 +15,10 @@
 // K-major (As[k][m], Bs[k][n]) so every MFMA operand read is 32 consecutive floats; the next
 // K-step is prefetched into registers under the current step's MFMAs.  K can be split over
 // gridDim.z: each split writes an fp32 partial slab and a second kernel adds the slabs in split
-// order (deterministic, no float atomics; reduce.hip).
+// order (deterministic, no float atomics; reduce.hip).  A K-split weight gradient of whole 128 x 128
+// tiles gets its slabs from the LDS-DMA ring kernel of gemm_wgrad.hip instead (same tile, same k
+// order, bit-identical partials); the kernel here stays for every other shape, for the bias-gradient
+// (CS) form and behind impl = HICGAT_GEMM_F32.
 #include <algorithm>
 #include <cstdlib>
 
@@ -236,9 +239,16 @@ __global__ void colsum_zero_kernel(float *out, int N, int accumulate) {
 
 // csum (weight gradients only): also db[m] (+)= sum_k A[k][m] (the CS kernels); the slab of split z
 // is then [M*N dW partials | M db partials].
+int gemm_wgrad_ring_launch(const float *A, int64_t lda, const float *B, int64_t ldb, int M, int N, int K, int kchunk,
+                           int splits, float *slab, int64_t slab_stride, hipStream_t s);   // gemm_wgrad.hip
+
+// ring (K-major A and B, 128 x 128 tiles, K split, no db): the partial slabs from the LDS-DMA ring
+// kernel of gemm_wgrad.hip when the problem fits it -- the same kchunk, slabs and slab sum, bit-identical
+// partials -- else from gemm_kernel as before.
 template <int BM, int BN, bool AK, bool BK_>
 static int launch(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc, int M, int N,
-                  int K, int splits, const float *bias, float *slab, int acc, hipStream_t s, float *csum = nullptr) {
+                  int K, int splits, const float *bias, float *slab, int acc, hipStream_t s, float *csum = nullptr,
+                  bool ring = false) {
   const int kchunk = ((K + splits - 1) / splits + GK - 1) / GK * GK;
   const dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN, splits);
   // float4 staging needs every float4 inside its operand row and 16-B aligned rows
@@ -252,7 +262,14 @@ static int launch(const float *A, int64_t lda, const float *B, int64_t ldb, floa
 #define HICGAT_GEMM_GO(V, D, C_)                                                                            \
   hipLaunchKernelGGL((gemm_kernel<BM, BN, AK, BK_, V, D, C_>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N, \
                      K, kchunk, bias, sl, stride, acc, cdst)
-  if (a_ok && b_ok && al) {
+  int ring_rc = HICGAT_EUNSUPPORTED;
+  if (ring && AK && BK_ && BM == 128 && BN == 128 && sl && !cs)
+    ring_rc = gemm_wgrad_ring_launch(A, lda, B, ldb, M, N, K, kchunk, splits, sl, stride, s);
+  if (ring_rc == HICGAT_OK) {
+    // the slabs are written; the slab sum below finishes C
+  } else if (ring_rc != HICGAT_EUNSUPPORTED) {
+    return ring_rc;
+  } else if (a_ok && b_ok && al) {
     constexpr bool db = !AK && BK_;   // double-buffered LDS: the dX layout (every layout measured: no gain)
     if (cs) HICGAT_GEMM_GO(true, db, AK);
     else HICGAT_GEMM_GO(true, db, false);
@@ -290,9 +307,14 @@ static int dispatch(const float *A, int64_t lda, const float *B, int64_t ldb, fl
   }
   // tall row-major problems (M = node rows): 64 x 128 tiles keep >= 2 blocks per CU in flight;
   // square-ish weight gradients (M, N = features, K = rows split): 128 x 128
-  // (128 x 128, 128 x 256 and 256 x 128 tiles for the tall problems measured slower, round 1)
-  if (M >= 128 && N >= 128 && M <= 1024)
-    return launch<128, 128, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
+  // (128 x 128, 128 x 256 and 256 x 128 tiles for the tall problems measured slower, round 1).
+  // A K-split weight gradient of whole 128 x 128 tiles (lin_l's dW after the gather) takes the
+  // LDS-DMA ring kernel (gemm_wgrad.hip); impl = HICGAT_GEMM_F32 keeps gemm_kernel (A/B, bitwise test)
+  if (M >= 128 && N >= 128 && M <= 1024) {
+    const bool ring = AK && BK_ && impl == HICGAT_GEMM_AUTO && splits > 1 && M % 128 == 0 && N % 128 == 0 &&
+                      N <= 1024 && lda % 4 == 0 && ldb % 4 == 0;
+    return launch<128, 128, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s, nullptr, ring);
+  }
   if (N >= 128) return launch<64, 128, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
   return launch<64, 64, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
 }

@@ -14,7 +14,11 @@ from .paramgrads import ColsumJob, WeightGradJob
 
 # name -> list of (start, end) torch.cuda.Event pairs recorded around launches (bench.py)
 TIMERS = None
-GEMM_F32 = 1   # include/hicgat.h HICGAT_GEMM_F32: fp32 MFMA (the only GEMM arithmetic)
+# include/hicgat.h: fp32 MFMA is the only GEMM arithmetic.  HICGAT_GEMM_AUTO lets the dispatch pick the
+# kernel (a K-split weight gradient of whole 128 x 128 tiles takes the LDS-DMA ring kernel);
+# HICGAT_GEMM_F32 keeps the register-staged gemm_kernel for it (bit-identical; A/B and tests)
+GEMM_AUTO = 0
+GEMM_F32 = 1
 
 
 class _timed:
@@ -64,7 +68,7 @@ class HipKernels:
 
     def __init__(self):
         self.lib = _lib.lib()
-        self.gemm_impl = GEMM_F32
+        self.gemm_impl = GEMM_AUTO
 
     # -- a2 ---------------------------------------------------------------------------------------
     def linear_att(self, x, W, att_l, att_r, h=None):
@@ -465,7 +469,7 @@ class HipKernels:
         ws = None
         impl = self.gemm_impl if impl is None else impl
         if splits is None:
-            splits = row_splits(M, N, K) if (not a_kmajor and impl == 1) else 1
+            splits = row_splits(M, N, K) if (not a_kmajor and impl in (GEMM_AUTO, GEMM_F32)) else 1
         if splits > 1:
             ws = _lib.workspace(self.lib.hicgat_gemm_workspace_bytes(M, N, splits), dev)
         with _timed(name):

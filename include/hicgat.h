@@ -413,8 +413,12 @@ int hicgat_truth_support(const float *T, int N, int64_t ldt, float background, i
  *   Linear forward Y = X W^T + b (0,0); input grad dX = dY W (0,1); weight grad dW = dY^T X (1,1).
  * accumulate != 0 adds into C (a parameter's .grad).  splits > 1 splits K over workgroups into fp32
  * slabs (workspace: hicgat_gemm_workspace_bytes; NULL, 0 with splits = 1) added in split order:
- * deterministic.  bias may be NULL.  impl names the matrix-core arithmetic: HICGAT_GEMM_AUTO (the
- * default) = HICGAT_GEMM_F32, the only one: v_mfma_f32_32x32x2_f32, fp32 products, fp32 accumulate.
+ * deterministic.  bias may be NULL.  impl: there is one matrix-core arithmetic, v_mfma_f32_32x32x2_f32
+ * (fp32 products, fp32 accumulate), and HICGAT_GEMM_AUTO (the default) and HICGAT_GEMM_F32 both run it
+ * and give the same bits.  AUTO leaves the kernel to the dispatch: a K-split weight gradient (1,1)
+ * of whole 128 x 128 tiles (M, N multiples of 128 up to 1024, lda and ldb multiples of 4, 16-byte
+ * aligned operands) takes the LDS-DMA ring kernel (gemm_wgrad.hip).  F32 keeps the register-staged
+ * gemm_kernel for that case too (A/B measurements, the bitwise test).
  * HICGAT_GEMM_X3 (a three-way bf16 operand split on the bf16 matrix cores, round 1-3) measured slower
  * per step and was removed: HICGAT_EUNSUPPORTED. */
 enum { HICGAT_GEMM_AUTO = 0, HICGAT_GEMM_F32 = 1, HICGAT_GEMM_X3 = 2 };

@@ -83,7 +83,7 @@ def main():
             fn.restype, fn.argtypes = res, args
         K = kernels.HipKernels.__new__(kernels.HipKernels)
         K.lib = lib
-        K.gemm_impl = 1              # fp32 MFMA
+        K.gemm_impl = kernels.GEMM_AUTO   # fp32 MFMA, the dispatch's kernel (what the step runs)
         kset.append((os.path.basename(path), K))
     jobs = {
         "gat_linear_att": lambda K: K.linear_att(x, W, al, ar),
