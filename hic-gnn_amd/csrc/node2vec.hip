@@ -85,19 +85,23 @@ __global__ __launch_bounds__(256) void n2v_walks_kernel(const int *__restrict__ 
 }
 
 // one wave per walk; D = 64 * VPL.  keep[v]: gensim's downsampling keep probability; cum[V]: the
-// unigram^0.75 cumulative table (cum[V-1] = its total).
+// unigram^0.75 cumulative table (cum[V-1] = its total).  nwaves: the waves that take walks (wave g
+// trains walks g, g + nwaves, ...); the last block's waves beyond it leave at once.
 template <int VPL>
 __global__ __launch_bounds__(256) void n2v_sgns_kernel(const int *__restrict__ walks, int nwalks, int L,
                                                        const float *__restrict__ keep,
                                                        const uint32_t *__restrict__ cum, int V, int window,
                                                        int negative, float alpha0, float alpha1, int epoch,
-                                                       int epochs, uint64_t seed, float *syn0, float *syn1) {
+                                                       int epochs, uint64_t seed, int nwaves, float *syn0,
+                                                       float *syn1) {
   constexpr int D = 64 * VPL;
   __shared__ int sent[4][1024];
   const int lane = lane_id(), wv = wave_in_block();
-  // grid-stride over walks: the caller bounds the waves in flight (Hogwild contention on a small
-  // vocabulary loses updates; the reference trains with one worker)
-  for (int w = blockIdx.x * 4 + wv; w < nwalks; w += gridDim.x * 4) {
+  // wave-stride over walks: the caller bounds the waves in flight (Hogwild contention on a small
+  // vocabulary loses updates; the reference trains with one worker: nwaves = 1 is sequential)
+  const int gw = blockIdx.x * 4 + wv;
+  if (gw >= nwaves) return;   // wave-uniform; the wave barriers below pair within a wave
+  for (int w = gw; w < nwalks; w += nwaves) {
   const float prog = ((float)epoch * nwalks + w) / ((float)epochs * nwalks);
   const float alpha = alpha0 - (alpha0 - alpha1) * prog;
   int *s = sent[wv];
@@ -128,7 +132,8 @@ __global__ __launch_bounds__(256) void n2v_sgns_kernel(const int *__restrict__ w
       }
       // the positive and the `negative` sampled targets: rows loaded together, the 8 dot products
       // reduced in one transpose reduce, then the updates applied in gensim's order (a target drawn
-      // twice in one pair reads its row once -- within Hogwild's own reordering)
+      // twice in one pair reads its row once and the later write wins -- within Hogwild's own
+      // reordering; tests/n2v_ref.py models it)
       int tg[8];
       float lab[8], s1[8][VPL], f[8];
 #pragma unroll
@@ -214,11 +219,12 @@ extern "C" int hicgat_n2v_sgns_epoch(const int32_t *walks, int nwalks, int walk_
   if (D % 64 || D < 64 || D > 1024) return HICGAT_EUNSUPPORTED;
   if (nwalks == 0) return HICGAT_OK;
   if (!walks || !keep_prob || !cum_table || !syn0 || !syn1) return HICGAT_EINVAL;
-  const dim3 grid((min(nwalks, max_waves) + 3) / 4), block(256);
+  const int nwaves = min(nwalks, max_waves);   // exactly this many waves take walks
+  const dim3 grid((nwaves + 3) / 4), block(256);
   hipStream_t s = (hipStream_t)stream;
 #define HICGAT_SGNS(VPL)                                                                                       \
   hipLaunchKernelGGL(n2v_sgns_kernel<VPL>, grid, block, 0, s, walks, nwalks, walk_length, keep_prob, cum_table, V, \
-                     window, negative, alpha0, alpha1, epoch, epochs, seed, syn0, syn1)
+                     window, negative, alpha0, alpha1, epoch, epochs, seed, nwaves, syn0, syn1)
   switch (D / 64) {
     case 1: HICGAT_SGNS(1); break;
     case 2: HICGAT_SGNS(2); break;

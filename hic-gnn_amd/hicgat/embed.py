@@ -129,9 +129,10 @@ def skipgram(walks, n_words, dimensions=512, window=25, epochs=5, negative=5, al
     st = _lib.stream(dev)
     if max_waves is None:
         # at most one concurrent walk per 64 words: sequential, like the reference's workers=1, for
-        # a Hi-C chromosome at 1 mb / 500 kb (58 / 114 loci); measured on chr19 1 mb, 1 vs 14
+        # a Hi-C chromosome at 1 mb / 500 kb (58 / 114 loci); measured on chr19 1 mb, 4 vs 14
         # concurrent walks give the same embedding structure (common-component share 0.984 vs
-        # 0.980, profiles/r03b_n2v_study.json) at 20 vs 5 s
+        # 0.980, profiles/r03b_n2v_study.json) at 20 vs 5 s; one walk at a time, as here, takes
+        # 80 s (the reference's 5 epochs over 2900 walks of 150 nodes, D = 512)
         max_waves = max(1, n_words // 64) if n_words < SMALL_VOCAB else max(1, min(4096, n_words // 4))
     for ep in range(epochs):
         _lib.check(lib.hicgat_n2v_sgns_epoch(P(walks), nwalks, L, P(t_keep), P(t_cum), n_words, dimensions, window,

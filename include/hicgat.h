@@ -670,7 +670,11 @@ int hicgat_kr_scale(const double *A, int64_t lda, int n, const double *x, double
  *   learning rate decaying linearly from alpha0 to alpha1 over `epochs`), gensim's downsampling
  *   (keep_prob[v]) and unigram^0.75 negative table (cum_table[V], cumulative), syn0 / syn1 [V, D]
  *   fp32 (D a multiple of 64, <= 1024; negative <= 7), updated Hogwild-style by at most max_waves walks in flight
- *   (one wave per walk; a small vocabulary wants few, the reference trains with one worker). */
+ *   (one wave per walk; a small vocabulary wants few, the reference trains with one worker):
+ *   exactly min(nwalks, max_waves) waves take walks, wave g the walks g, g + that many, ..., so
+ *   max_waves = 1 trains the walks one after the other, in order, and is deterministic.  Within one
+ *   (centre, context) pair all target rows are read before any is written: a target drawn twice
+ *   in the pair reads its row once, and the later write wins. */
 int hicgat_n2v_walks(const int32_t *rowptr, const int32_t *col, const float *cum_weights, int N,
                      const int32_t *starts, int nwalks, int walk_length, float p, float q, uint64_t seed,
                      int32_t *walks, hicgat_stream_t stream);
