@@ -296,26 +296,49 @@ int gemm_tall_launch(bool b_kmajor, const float *A, int64_t lda, const float *B,
 // FLOP than the 20000-row GEMM).  The single-GPU shapes (>= 250 tiles) keep the tall kernel.
 static int64_t tall_min_tiles() { return 192; }
 
+// ---- every tile size of the family, and which one a problem gets ------------------------------------
+constexpr int kTallBM = 160, kTallBN = 128;   // gemm_tall.hip's tile (its TBM x TBN)
+constexpr int kTallMinM = 1024;               // node-row problems: at least this many rows
+constexpr int kRowsBM = 64, kRowsBN = 128;    // the grouped node-row kernel (hicgat_gemm_rows_grouped)
+constexpr int kGroupTile = 128;               // the grouped weight-gradient kernel: square tiles
+constexpr int kSplitMinDepth = 128;           // a K-split node-row GEMM: every chunk at least this deep
+
+struct GemmTile {
+  bool tall;    // gemm_tall.hip's kernel is the candidate (it may decline: then bm x bn)
+  int bm, bn;   // gemm_kernel's tile: 128 x 128, 64 x 128 or 64 x 64
+};
+
+// The tile of node-row problems: 64 x 128 keeps >= 2 blocks per CU in flight (128 x 128, 128 x 256
+// and 256 x 128 tiles for the tall problems measured slower, round 1); 64 x 64 below 128 columns.
+static GemmTile rows_tile(int N) { return N >= 128 ? GemmTile{false, 64, 128} : GemmTile{false, 64, 64}; }
+
+// The one tile rule: dispatch<>, hicgat_gemm_wgrad and the split queries below all ask here.
+static GemmTile tile_for(bool a_kmajor, int M, int N, int splits) {
+  // tall node-row problems (Linear forward, input gradient): the 160x128 LDS-DMA kernel (gemm_tall.hip)
+  const bool tall = !a_kmajor && splits == 1 && M >= kTallMinM &&
+                    (int64_t)((M + kTallBM - 1) / kTallBM) * (N / kTallBN) >= tall_min_tiles();
+  // square-ish weight gradients (M, N = features, K = rows split): 128 x 128
+  GemmTile t = (M >= 128 && N >= 128 && M <= 1024) ? GemmTile{false, 128, 128} : rows_tile(N);
+  t.tall = tall;
+  return t;
+}
+
 template <bool AK, bool BK_>
 static int dispatch(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc, int M, int N,
                     int K, int splits, const float *bias, float *slab, int acc, int impl, hipStream_t s) {
-  // tall node-row problems (Linear forward, input gradient): the 160x128 LDS-DMA kernel (gemm_tall.hip)
-  if (!AK && splits == 1 && M >= 1024 &&
-      (int64_t)((M + 159) / 160) * (N / 128) >= tall_min_tiles()) {
+  const GemmTile t = tile_for(AK, M, N, splits);
+  if (t.tall) {
     const int rc = gemm_tall_launch(BK_, A, lda, B, ldb, C, ldc, M, N, K, bias, acc, s);
     if (rc != HICGAT_EUNSUPPORTED) return rc;
   }
-  // tall row-major problems (M = node rows): 64 x 128 tiles keep >= 2 blocks per CU in flight;
-  // square-ish weight gradients (M, N = features, K = rows split): 128 x 128
-  // (128 x 128, 128 x 256 and 256 x 128 tiles for the tall problems measured slower, round 1).
   // A K-split weight gradient of whole 128 x 128 tiles (lin_l's dW after the gather) takes the
   // LDS-DMA ring kernel (gemm_wgrad.hip); impl = HICGAT_GEMM_F32 keeps gemm_kernel (A/B, bitwise test)
-  if (M >= 128 && N >= 128 && M <= 1024) {
+  if (t.bm == 128) {
     const bool ring = AK && BK_ && impl == HICGAT_GEMM_AUTO && splits > 1 && M % 128 == 0 && N % 128 == 0 &&
                       N <= 1024 && lda % 4 == 0 && ldb % 4 == 0;
     return launch<128, 128, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s, nullptr, ring);
   }
-  if (N >= 128) return launch<64, 128, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
+  if (t.bn == 128) return launch<64, 128, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
   return launch<64, 64, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
 }
 
@@ -325,7 +348,7 @@ static int dispatch(const float *A, int64_t lda, const float *B, int64_t ldb, fl
 // workgroup counts, then (tile row, tile column, K chunk).  One K-chunk depth for all jobs, so every
 // workgroup has the same MFMA work.  A job whose operands cannot be read as float4 (dense3: M = 3)
 // takes the scalar-staged path of the same tile in the same launch.
-constexpr int kMaxWJobs = 16, kMaxCJobs = 32, kGroupTile = 128;
+constexpr int kMaxWJobs = 16, kMaxCJobs = 32;
 constexpr int64_t WEIGHTED_LG1_ROWS = 1024;   // weighted column-sum jobs taller than this: 2 lanes per row group
 // jobs of at most this many rows (the split-K slabs: 6-16 splits) take one lane per 4 columns with
 // every row in that lane (lg = 8: 1024 columns per block, no LDS combine) instead of 4 row groups of
@@ -520,7 +543,7 @@ __global__ __launch_bounds__(256, kOcc64) void gemm_rows_grouped_kernel(const RJ
   const int bz = local / per, rem = local - bz * per, bx = rem % J.tm, by = rem / J.tm;
   // splits = 1: the tile writes C (+ bias, + relu copy) itself and no reduce launch follows
   const bool direct = jobs.splits == 1;
-  gemm_tile<64, 128, false, B_KM, true, !B_KM ? false : true, false>(
+  gemm_tile<kRowsBM, kRowsBN, false, B_KM, true, !B_KM ? false : true, false>(
       J.a, J.lda, J.b, J.ldb, J.c, J.ldc, J.M, J.N, J.K, J.kchunk, direct ? J.bias : nullptr,
       direct ? nullptr : J.slab, (int64_t)J.M * J.N, 0, nullptr, bx, by, bz, direct ? J.cr : nullptr, J.ldr);
 }
@@ -549,6 +572,17 @@ __global__ __launch_bounds__(256) void rows_reduce_kernel(const RJobs jobs) {
 }  // namespace hicgat
 
 using namespace hicgat;
+
+// Enough K chunks for ~target_wgs workgroups over all jobs, each chunk >= kSplitMinDepth deep (the
+// jobs share one split count: the first job's K bounds it).
+extern "C" int hicgat_gemm_rows_grouped_splits(const hicgat_gemm_job *jobs, int n, int target_wgs) {
+  if (n <= 0 || !jobs || target_wgs <= 0) return 1;
+  int64_t wgs = 0;
+  for (int i = 0; i < n; ++i)
+    wgs += (int64_t)((jobs[i].M + kRowsBM - 1) / kRowsBM) * ((jobs[i].N + kRowsBN - 1) / kRowsBN);
+  wgs = std::max<int64_t>(1, wgs);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(jobs[0].K / kSplitMinDepth, (target_wgs + wgs - 1) / wgs));
+}
 
 extern "C" size_t hicgat_gemm_rows_grouped_workspace_bytes(const hicgat_gemm_job *jobs, int n, int splits) {
   if (n <= 0 || !jobs || splits <= 1) return 0;   // one chunk: the tiles write C directly
@@ -592,8 +626,8 @@ extern "C" int hicgat_gemm_rows_grouped(const hicgat_gemm_job *jobs, int n, int 
     J.N = a.N;
     J.K = a.K;
     J.kchunk = ((a.K + splits - 1) / splits + GK - 1) / GK * GK;
-    J.tm = (a.M + 63) / 64;
-    J.tn = (a.N + 127) / 128;
+    J.tm = (a.M + kRowsBM - 1) / kRowsBM;
+    J.tn = (a.N + kRowsBN - 1) / kRowsBN;
     J.slab = slab;
     slab += (size_t)splits * a.M * a.N;
     J.wg0 = wg;
@@ -731,6 +765,40 @@ extern "C" int hicgat_param_grads_grouped(const hicgat_wgrad_job *w, int nw, con
   return HICGAT_OK;
 }
 
+// K-split of a node-row GEMM (Linear forward / input gradient: M = rows) that would leave the chip
+// mostly idle: a rank's shard of the multi-GPU step (M ~ 2700 rows at P = 8) gives the 64 x 128
+// kernel 43 x 4 = 172 workgroups with the whole K = 512 each, one per CU, latency-bound per K-step
+// (38 us for 1.4 GFLOP, profiles/r03f_simprof_*_P8_rank0_timeline.txt; split in 3: 28 + 7 us for the slab
+// sum).  Split over K until ~512 workgroups are in flight (each split >= 128 deep), partial slabs
+// added in split order (deterministic).  The tall 160 x 128 kernel split the same way (a grid.y of
+// K-chunks into slabs) measured slower at these shapes (r03i: 23-33 + 8 us) and was not kept.
+// Shapes that fill the chip on their own -- every single-GPU shape at N = 20000 (the tall kernel,
+// or >= 256 tiles) -- keep splits = 1.
+// The workgroups are counted in rows_tile(N) tiles: at M = 1024 exactly (N >= 128) tile_for gives
+// the split problem 128 x 128 tiles, half as many workgroups as counted here.  Kept as measured.
+extern "C" int hicgat_gemm_row_splits(int M, int N, int K) {
+  constexpr int64_t kFull = 256, kTarget = 512;   // workgroups: a full chip (one per CU) / aimed at by the split
+  if (M < kTallMinM || K < 2 * kSplitMinDepth || N <= 0) return 1;
+  if (tile_for(false, M, N, 1).tall) return 1;
+  const GemmTile t = rows_tile(N);
+  const int64_t wgs = (int64_t)((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
+  if (wgs >= kFull) return 1;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(K / kSplitMinDepth, (kTarget + wgs - 1) / wgs));
+}
+
+// K-split of a weight-gradient GEMM whose K is the node count: about target_wgs workgroups, each
+// split at least 256 rows deep.  The tiles are counted by a rule of its own, kept as it is because
+// the targets were measured with it: tile_for's row height without its M <= 1024 bound (M > 1024
+// with N >= 128 counts 128-row tiles where the dispatch runs 64 x 128), and columns in tiles as wide
+// as that height (M < 128 <= N counts 64 x 64 tiles where the dispatch runs 64 x 128).
+extern "C" int hicgat_gemm_wgrad_splits(int M, int N, int K, int target_wgs) {
+  constexpr int kMinDepth = 256;
+  if (M <= 0 || N <= 0) return 1;
+  const int b = tile_for(true, std::min(M, 128), N, 2).bm;   // the first 128 rows: inside the M bound
+  const int64_t tiles = (int64_t)((M + b - 1) / b) * ((N + b - 1) / b);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(K / kMinDepth, target_wgs / tiles));
+}
+
 extern "C" size_t hicgat_gemm_workspace_bytes(int M, int N, int splits) {
   return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
 }
@@ -769,10 +837,10 @@ extern "C" int hicgat_gemm_wgrad(int M, int N, int K, const float *dY, int64_t l
     return HICGAT_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   float *slab = static_cast<float *>(workspace);
-  // the dispatch of hicgat_gemm's fp32 path for the (K-major, K-major) layout
-  if (M >= 128 && N >= 128 && M <= 1024)
+  const GemmTile t = tile_for(true, M, N, splits);
+  if (t.bm == 128)
     return launch<128, 128, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
-  if (N >= 128) return launch<64, 128, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
+  if (t.bn == 128) return launch<64, 128, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
   return launch<64, 64, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
 }
 

@@ -181,6 +181,7 @@ __device__ __forceinline__ void ln_rows(const float *__restrict__ Ys, int lds, c
 // P = 8 shard's forward; 16: rank step 0.438-0.440 vs 0.448 ms -- a rank's shard at P = 8 has 169
 // workgroups for 256 CUs, one each).  The LayerNorm parameter partials are one row per wave.
 constexpr int kTailWaves = 16;   // 16: 0.438 / 0.440 vs 0.448 ms per P = 8 rank step (profiles/r04k_sim_ab.txt)
+constexpr int kTailBwdRows = 16; // RB of the backward launch: one LayerNorm partial row per workgroup
 // HEADS (the sharded aggregate-first GATConv, gat_xagg.hip): the tail's input rows are formed here
 // from the two heads' aggregates, out^h = xa^h W_h^T + b^h (xa^h = x + h * xa_hs, row stride ldx; W_h
 // = rows 256h .. of lin_l's weight Wh [512][512]), written as Y0 (pre-activation) and O = relu(Y0)
@@ -891,8 +892,11 @@ extern "C" int hicgat_tail_fwd_fused_heads(const float *xa, int64_t ld_xa, int64
 
 extern "C" int hicgat_tail_bwd_waves(void) { return kTailWaves; }
 
+extern "C" int hicgat_tail_bwd_partial_rows(int M) { return M <= 0 ? 0 : (M + kTailBwdRows - 1) / kTailBwdRows; }
+
 extern "C" size_t hicgat_tail_bwd_workspace_bytes(int M, int W) {
-  return M <= 0 ? 16 : (size_t)((M + 15) / 16) * 2 * W * sizeof(float);   // one [2W] row per workgroup
+  // one [2W] row per workgroup
+  return M <= 0 ? 16 : (size_t)hicgat_tail_bwd_partial_rows(M) * 2 * W * sizeof(float);
 }
 
 namespace {
@@ -908,7 +912,7 @@ int tail_bwd_go(const float *dcoords, int M, const float *Y1, const float *st1, 
                 const float *g1, const float *be1, const float *g2, const float *be2, const float *g3,
                 const float *be3, float *dx, float *dY1, float *dY2, float *dy3, void *ws1, void *ws2, void *ws3,
                 const float *Wh, const TailHeadsBwd &hh, hipStream_t stream) {
-  constexpr int RB = 16, NW = kTailWaves;
+  constexpr int RB = kTailBwdRows, NW = kTailWaves;
   // [As | Bs] row images + the [NW][2 x 256] LayerNorm partial scratch
   constexpr int kBwdLds = (2 * RB * XS + NW * 2 * 256) * (int)sizeof(float);
   static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&tail_bwd_kernel<RB, NW, HEADS, PK, ROWS>),

@@ -109,10 +109,13 @@ SIGNATURES = {
     "hicgat_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int,
                             c_int, c_int, c_p, c_sz, c_p]),
     "hicgat_gemm_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "hicgat_gemm_row_splits": (c_int, [c_int, c_int, c_int]),
     "hicgat_gemm_wgrad": (c_int, [c_int, c_int, c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p,
                                   c_sz, c_p]),
     "hicgat_gemm_wgrad_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "hicgat_gemm_wgrad_splits": (c_int, [c_int, c_int, c_int, c_int]),
     "hicgat_gemm_rows_grouped_workspace_bytes": (c_sz, [c_gjobs, c_int, c_int]),
+    "hicgat_gemm_rows_grouped_splits": (c_int, [c_gjobs, c_int, c_int]),
     "hicgat_gemm_rows_grouped": (c_int, [c_gjobs, c_int, c_int, c_int, c_p, c_sz, c_p]),
     "hicgat_param_grads_workspace_bytes": (c_sz, [c_wjobs, c_int, c_int]),
     "hicgat_param_grads_grouped": (c_int, [c_wjobs, c_int, c_cjobs, c_int, c_int, c_p, c_sz, c_p]),
@@ -130,6 +133,7 @@ SIGNATURES = {
     "hicgat_tail_pack": (c_int, [c_p, c_p, c_p, c_p, c_sz, c_p]),
     "hicgat_tail_fwd_fused": (c_int, [c_p, c_i64, c_int] + [c_p] * 14 + [c_f] + [c_p] * 10 + [c_p, c_p]),
     "hicgat_tail_bwd_waves": (c_int, []),
+    "hicgat_tail_bwd_partial_rows": (c_int, [c_int]),
     "hicgat_tail_bwd_workspace_bytes": (c_sz, [c_int, c_int]),
     "hicgat_tail_bwd_fused": (c_int, [c_p, c_int] + [c_p] * 16 + [c_p] * 4 + [c_p, c_sz] * 3 + [c_p, c_p]),
     "hicgat_tail_fwd_fused_heads": (c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_int] + [c_p] * 14 + [c_f]

@@ -39,28 +39,13 @@ class _timed:
 
 P = _lib.ptr
 
-# K-split of a node-row GEMM (Linear forward / input gradient: M = rows) that would leave the chip
-# mostly idle: a rank's shard of the multi-GPU step (M ~ 2700 rows at P = 8) gives the 64 x 128
-# kernel 43 x 4 = 172 workgroups with the whole K = 512 each, one per CU, latency-bound per K-step
-# (38 us for 1.4 GFLOP, profiles/r03f_simprof_*_P8_rank0_timeline.txt; split in 3: 28 + 7 us for the slab
-# sum).  Split over K until ~512 workgroups are in flight (each split >= 128 deep), partial slabs
-# added in split order (deterministic).  The tall 160 x 128 kernel split the same way (a grid.y of
-# K-chunks into slabs) measured slower at these shapes (r03i: 23-33 + 8 us) and was not kept.
-# Shapes that fill the chip on their own -- every single-GPU shape at N = 20000 (the tall kernel,
-# or >= 256 tiles) -- keep splits = 1.  HICGAT_ROW_SPLIT=0: off (A/B).
+# K-split of a node-row GEMM that would leave the chip mostly idle (a rank's shard of the multi-GPU
+# step): the library's rule, hicgat_gemm_row_splits (gemm.hip).  HICGAT_ROW_SPLIT=0: off (A/B).
 ROW_SPLIT = os.environ.get("HICGAT_ROW_SPLIT", "1") != "0"
-_TALL_MIN_TILES = 192   # gemm.hip tall_min_tiles(): the tall kernel takes shapes with at least this many tiles
 
 
 def row_splits(M, N, K):
-    if not ROW_SPLIT or M < 1024 or K < 256:
-        return 1
-    if -(-M // 160) * (N // 128) >= _TALL_MIN_TILES:      # the tall kernel takes it (gemm.hip dispatch)
-        return 1
-    wgs = -(-M // 64) * -(-N // (128 if N >= 128 else 64))
-    if wgs >= 256:
-        return 1
-    return max(1, min(K // 128, -(-512 // wgs)))
+    return 1 if not ROW_SPLIT else _lib.load().hicgat_gemm_row_splits(M, N, K)
 
 
 class HipKernels:
@@ -547,10 +532,9 @@ class HipKernels:
 
     def gemm_rows_grouped(self, jobs, b_kmajor, splits=None, name="gemm_grouped"):
         """include/hicgat.h hicgat_gemm_rows_grouped: ``jobs`` = [(A [M, K], B, C [M, N], bias or None,
-        C_relu or None)], B [N, K] (``b_kmajor`` 0) or [K, N] (1).  ``splits`` None: enough K chunks
-        for ~512 workgroups over all jobs (each chunk >= 128 deep)."""
+        C_relu or None)], B [N, K] (``b_kmajor`` 0) or [K, N] (1).  ``splits`` None: the library's
+        K split for ``ROWS_WGS`` workgroups over all jobs (hicgat_gemm_rows_grouped_splits)."""
         G = (_lib.GemmJob * len(jobs))()
-        wgs = 0
         for k, (A, B, C, bias, Cr) in enumerate(jobs):
             M, Kd = A.shape
             N = C.shape[1]
@@ -560,9 +544,8 @@ class HipKernels:
             G[k] = _lib.GemmJob(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0),
                                 None if Cr is None else Cr.data_ptr(), 0 if Cr is None else Cr.stride(0),
                                 None if bias is None else bias.data_ptr(), M, N, Kd)
-            wgs += -(-M // 64) * -(-N // 128)
         if splits is None:
-            splits = max(1, min(jobs[0][0].shape[1] // 128, -(-self.ROWS_WGS // max(1, wgs)))) if self.ROWS_WGS else 1
+            splits = self.lib.hicgat_gemm_rows_grouped_splits(G, len(jobs), self.ROWS_WGS)
         dev = jobs[0][2].device
         ws = _lib.workspace(self.lib.hicgat_gemm_rows_grouped_workspace_bytes(G, len(jobs), splits), dev)
         with _timed(name):
@@ -673,7 +656,7 @@ class HipKernels:
 
     def tail_partial_rows(self, M):
         """Rows of LayerNorm partials hicgat_tail_bwd_fused leaves per workspace: one per workgroup."""
-        return -(-M // 16)
+        return int(self.lib.hicgat_tail_bwd_partial_rows(M))
 
     # -- LayerNorm -> act (+ res) (-> LayerNorm) and the elementwise act (ln_act.hip) ---------------
     def ln_act_workspace(self, W, second_norm, device):

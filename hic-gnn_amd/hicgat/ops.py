@@ -235,11 +235,8 @@ _DW_BLOCKS = int(os.environ.get("HICGAT_DW_BLOCKS", "256"))
 
 def _splits(m, n, k, target=None):
     """K-split for a weight-gradient GEMM whose K is the node count: enough workgroups to fill
-    the 256 CUs, each split at least 256 rows deep."""
-    target = _DW_BLOCKS if target is None else target
-    bm = 128 if (m >= 128 and n >= 128) else 64
-    tiles = -(-m // bm) * -(-n // bm)
-    return max(1, min(k // 256, target // tiles))
+    the 256 CUs, each split at least 256 rows deep (the library's hicgat_gemm_wgrad_splits)."""
+    return _lib.load().hicgat_gemm_wgrad_splits(m, n, k, _DW_BLOCKS if target is None else target)
 
 
 def weight_grad(K, dy, x, out=None, accumulate=False, impl=None):

@@ -426,6 +426,13 @@ int hicgat_gemm(int a_kmajor, int b_kmajor, int M, int N, int K, const float *A,
                 const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
                 int splits, int impl, void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
 size_t hicgat_gemm_workspace_bytes(int M, int N, int splits);
+/* The `splits` a caller should hand hicgat_gemm for a node-row problem (a_kmajor = 0: Linear forward,
+ * input gradient; M = rows): 1 when the problem fills the chip unsplit (the tall 160 x 128 kernel
+ * takes it, or its 64-row tiles are >= 256 workgroups) and for M < 1024 or K < 256; else enough K
+ * chunks, each >= 128 deep, for ~512 workgroups (a rank's shard of the multi-GPU step).  Derived from
+ * the dispatch's own tile rule.  A pure function of its arguments: no stream, no HIP call, no GPU
+ * needed (as hicgat_pairdist_num_tiles). */
+int hicgat_gemm_row_splits(int M, int N, int K);
 /* Weight AND bias gradient of a Linear in one GEMM (replaces the dW GEMM + bias column sum of the
  * Linear backward, torch.nn.Linear via ATen addmm_backward / sum(0), models.py:637-659):
  *   dW[M,N] (+)= dY^T X  (dY [K,M] and X [K,N] row-major, K = node rows),
@@ -438,6 +445,10 @@ int hicgat_gemm_wgrad(int M, int N, int K, const float *dY, int64_t ldy, const f
                       int64_t lddw, float *db, int accumulate, int splits, void *workspace, size_t workspace_bytes,
                       hicgat_stream_t stream);
 size_t hicgat_gemm_wgrad_workspace_bytes(int M, int N, int splits);
+/* The `splits` a caller should hand hicgat_gemm_wgrad (or hicgat_gemm's (1,1) layout) for dW [M, N]
+ * over K node rows: about target_wgs workgroups in all, every split at least 256 rows deep, at
+ * least 1.  Pure host arithmetic: no stream, no HIP call, no GPU needed. */
+int hicgat_gemm_wgrad_splits(int M, int N, int K, int target_wgs);
 /* ---- grouped parameter gradients (one training step's dW / db / LayerNorm sums in two launches) ----
  * Replaces the per-Linear autograd weight-gradient calls (the ATen mm of dY^T X and the bias sum
  * behind every torch.nn.Linear.backward in models.py:637-659, and GATConv lin_l's) when a
@@ -497,6 +508,10 @@ typedef struct hicgat_gemm_job {
   int M, N, K;
 } hicgat_gemm_job;
 size_t hicgat_gemm_rows_grouped_workspace_bytes(const hicgat_gemm_job *jobs, int n, int splits);
+/* The `splits` for these jobs (only M, N, K are read): enough K chunks, each >= 128 deep by the first
+ * job's K, for about target_wgs 64 x 128 workgroups over all jobs; target_wgs = 0 (or no job): 1, the
+ * unsplit form.  Pure host arithmetic: no stream, no HIP call, no GPU needed. */
+int hicgat_gemm_rows_grouped_splits(const hicgat_gemm_job *jobs, int n, int target_wgs);
 int hicgat_gemm_rows_grouped(const hicgat_gemm_job *jobs, int n, int b_kmajor, int splits, void *workspace,
                              size_t workspace_bytes, hicgat_stream_t stream);
 /* out[n] = sum_k A[k][n] over K rows (a Linear bias gradient), deterministic two-stage. */
@@ -588,8 +603,12 @@ int hicgat_tail_pack(const float *W1c, const float *W2c, const float *Wh, void *
  * [0, ceil(M/16)) of a [.][2W] = [dgamma | dbeta] matrix, one per 16-row workgroup (its waves'
  * partials added in wave order; the rows' column sums, e.g. hicgat_colsum, are dgamma / dbeta); each
  * workspace at least hicgat_tail_bwd_workspace_bytes(M, W) for W = 256 / 128 / 64.
- * hicgat_tail_bwd_waves(): the waves per workgroup of both tail kernels. */
+ * hicgat_tail_bwd_waves(): the waves per workgroup of both tail kernels.
+ * hicgat_tail_bwd_partial_rows(M): the rows of partials each workspace holds after the call, one per
+ * workgroup (ceil(M / the kernel's row block); 0 for M <= 0) -- what the caller's column sums read.
+ * Pure host arithmetic: no stream, no HIP call, no GPU needed. */
 int hicgat_tail_bwd_waves(void);
+int hicgat_tail_bwd_partial_rows(int M);
 size_t hicgat_tail_bwd_workspace_bytes(int M, int W);
 int hicgat_tail_bwd_fused(const float *dcoords, int M, const float *Y1, const float *st1, const float *Y2,
                           const float *st2, const float *y3, const float *st3, const float *W4, const float *W3,
