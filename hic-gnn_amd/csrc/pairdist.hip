@@ -796,6 +796,447 @@ __global__ __launch_bounds__(256) void pairdist_fwd_kernel(const float *__restri
   D[(size_t)i * ldd + j] = i == j ? 0.f : sqrtf(fmaf(dx, dx, fmaf(dy, dy, dz * dz)));
 }
 
+// ---- moment-dependent losses (mse + alpha (1 - r), rmse, scale-invariant mse) ---------------------
+// Their derivative per pair is g_ij = A d_ij + B t_ij + C with A, B, C functions of the global
+// moments, which are only known after the pass.  With u_ij = (c_i - c_j) / d_ij (0 where d_ij = 0):
+//   dc_i = sum_j g_ij u_ij = -B R_i + (A + B) U_i + C W_i,
+//   R_i = sum_j (d_ij - t_ij) u_ij,  U_i = sum_j (c_i - c_j) = N c_i - sum_j c_j,  W_i = sum_j u_ij,
+// so one tile pass accumulates R and W (and all the moments) without A, B, C; a per-row combine
+// applies them in fp64 after the moments are final (mloss_finalize_kernel).
+enum { MLOSS_PEARSON = HICGAT_MLOSS_PEARSON, MLOSS_RMSE = HICGAT_MLOSS_RMSE, MLOSS_SI_MSE = HICGAT_MLOSS_SI_MSE };
+
+constexpr int kMPlanes = 6;   // row partial planes in LDS: R x/y/z, W x/y/z
+constexpr int kMSlabs = 4;    // float4 slabs per tile: R rows, R columns, W rows, W columns
+constexpr double kVarFloor = 0x1.0p-20;   // see mloss_finalize_kernel
+
+// Per-thread accumulators of one tile, packed: the column partials of R and W for the thread's 8
+// columns (4 float2 each) and the six pair moments.
+struct MTileAcc {
+  f2 ax[4], ay[4], az[4], bx[4], by[4], bz[4];
+  f2 L, sd, sdd, sdt, st, stt;
+  double dg = 0.0, sg = 0.0;   // sum T_ii^2, sum T_ii (diagonal tiles of the dense form), exact products:
+                               // si_mse subtracts the squared mean from them
+};
+
+// The thread's 8 rows x 8 columns in packed fp32.  MASK (diagonal and edge tiles): pairs outside
+// i < j < N get t = 0 and d, 1/d scaled by 0, so every sum below leaves them out with no select in
+// the arithmetic.  d^2 == 0 (coincident points): inv = 2^50 and d = 0 exactly, dx = dy = dz = 0, so
+// neither R nor W gets a term -- u_ij = 0 there.  BG: t = bg at every pair, no T read.
+template <bool MASK, bool BG>
+__device__ __forceinline__ void mloss_rows(const float *__restrict__ T, int64_t ldt, bool vec, int N, int I, int J,
+                                           float bg, const float (*sc)[BT][3], int tx, int ty, const f2 *cx2,
+                                           const f2 *cy2, const f2 *cz2, int gj0, MTileAcc &A, float *rowpart) {
+  const f2 z2 = f2{0.f, 0.f}, eps2 = f2{0x1.0p-100f, 0x1.0p-100f};
+#pragma unroll 2
+  for (int k = 0; k < 8; ++k) {
+    const int lr = ty * 4 + (k & 3) + (k >> 2) * 64;
+    const int gi = I * BT + lr;
+    const f2 rx = f2{sc[0][lr][0], sc[0][lr][0]}, ry = f2{sc[0][lr][1], sc[0][lr][1]},
+             rz = f2{sc[0][lr][2], sc[0][lr][2]};
+    float tv[8];
+    if constexpr (BG) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) tv[q] = bg;
+    } else if (vec) {   // block-uniform: two 16-B loads (a 16-lane row sweeps 256 B); rows past N clamped, masked below
+      const float *trow = T + (size_t)min(gi, N - 1) * ldt + (size_t)J * BT + tx * 4;
+      const float4 a = *reinterpret_cast<const float4 *>(trow);
+      const float4 b = *reinterpret_cast<const float4 *>(trow + 64);
+      tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w;
+      tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int gj = gj0 + (q & 3) + (q >> 2) * 64;
+        tv[q] = (gi < N && gj < N) ? T[(size_t)gi * ldt + gj] : 0.f;
+      }
+    }
+    float mk[8];
+    if constexpr (MASK) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int gj = gj0 + (q & 3) + (q >> 2) * 64;
+        const bool in = gi < N && gj < N;
+        if (!BG && in && gi == gj) {   // the diagonal entry: (0 - T_ii)^2 of the all-entries mean, and T_ii
+          A.dg += (double)tv[q] * (double)tv[q];
+          A.sg += (double)tv[q];
+        }
+        const bool valid = in && (I != J || gi < gj);
+        mk[q] = valid ? 1.f : 0.f;
+        tv[q] = valid ? tv[q] : 0.f;
+      }
+    }
+    f2 px = z2, py = z2, pz = z2, qx = z2, qy = z2, qz = z2;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const f2 dx = rx - cx2[h], dy = ry - cy2[h], dz = rz - cz2[h];
+      const f2 d2 = __builtin_elementwise_fma(dx, dx, __builtin_elementwise_fma(dy, dy, dz * dz));
+      const f2 d2e = d2 + eps2;
+      f2 inv = f2{__builtin_amdgcn_rsqf(d2e.x), __builtin_amdgcn_rsqf(d2e.y)};
+      if constexpr (MASK) inv *= f2{mk[2 * h], mk[2 * h + 1]};
+      const f2 d = d2 * inv;
+      const f2 t = f2{tv[2 * h], tv[2 * h + 1]};
+      const f2 r = d - t;
+      A.L = __builtin_elementwise_fma(r, r, A.L);
+      A.sd += d;
+      A.sdd = __builtin_elementwise_fma(d, d, A.sdd);
+      if constexpr (!BG || MASK) {   // BG interior: t = bg at all 64 pairs, these three by count below
+        A.sdt = __builtin_elementwise_fma(d, t, A.sdt);
+        A.st += t;
+        A.stt = __builtin_elementwise_fma(t, t, A.stt);
+      }
+      const f2 w = r * inv;
+      px = __builtin_elementwise_fma(w, dx, px);
+      py = __builtin_elementwise_fma(w, dy, py);
+      pz = __builtin_elementwise_fma(w, dz, pz);
+      A.ax[h] = __builtin_elementwise_fma(-w, dx, A.ax[h]);
+      A.ay[h] = __builtin_elementwise_fma(-w, dy, A.ay[h]);
+      A.az[h] = __builtin_elementwise_fma(-w, dz, A.az[h]);
+      qx = __builtin_elementwise_fma(inv, dx, qx);
+      qy = __builtin_elementwise_fma(inv, dy, qy);
+      qz = __builtin_elementwise_fma(inv, dz, qz);
+      A.bx[h] = __builtin_elementwise_fma(-inv, dx, A.bx[h]);
+      A.by[h] = __builtin_elementwise_fma(-inv, dy, A.by[h]);
+      A.bz[h] = __builtin_elementwise_fma(-inv, dz, A.bz[h]);
+    }
+    // the thread's 8-column partial of row lr; the 16 of a row are added in tx order at the end
+    float *rp = rowpart + lr * kRowPad + tx;
+    rp[0] = px.x + px.y;
+    rp[kRowPlane] = py.x + py.y;
+    rp[2 * kRowPlane] = pz.x + pz.y;
+    rp[3 * kRowPlane] = qx.x + qx.y;
+    rp[4 * kRowPlane] = qy.x + qy.y;
+    rp[5 * kRowPlane] = qz.x + qz.y;
+  }
+}
+
+// One 256-thread block per upper-triangle 128x128 tile, whole matrix only.  Writes, per tile, four
+// [128] float4 slabs (R row partials, R column partials, W row partials, W column partials) and one
+// moment record of 8 doubles: sum (d-t)^2, sum d, sum d^2, sum dt, sum t, sum t^2, sum T_ii^2,
+// sum T_ii.  Two workgroups per CU (256 VGPRs, ~77 KB of LDS).
+template <bool BG>
+__global__ __launch_bounds__(256, 2) void pairdist_mloss_tile_kernel(const float *__restrict__ coords,
+                                                                     const float *__restrict__ T, int N, int64_t ldt,
+                                                                     int vec, int nb, float4 *__restrict__ part,
+                                                                     double *__restrict__ mom, float bg,
+                                                                     float4 *__restrict__ cpad) {
+  __shared__ float sc[2][BT][3];
+  __shared__ float colred[kMPlanes][4][BT];
+  __shared__ double mred[4][8];
+  __shared__ __attribute__((aligned(16))) float rowpart[kMPlanes * kRowPlane];
+  const int64_t t = blockIdx.x;
+  int I, J;
+  tri_decode(t, nb, I, J);
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lane = tid & 63, wv = tid >> 6;
+  for (int k = tid; k < 2 * BT; k += 256) {
+    const int which = k / BT, li = k % BT;
+    const int g = (which ? J : I) * BT + li;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (g < N) {
+      x = coords[3 * (size_t)g];
+      y = coords[3 * (size_t)g + 1];
+      z = coords[3 * (size_t)g + 2];
+    }
+    sc[which][li][0] = x;
+    sc[which][li][1] = y;
+    sc[which][li][2] = z;
+    // the diagonal tile of row block I writes its rows' float4 copy for the support pass that follows
+    if (cpad && I == J && which == 0 && g < N) cpad[g] = make_float4(x, y, z, 0.f);
+  }
+  __syncthreads();
+
+  f2 cx2[4], cy2[4], cz2[4];
+  const int gj0 = J * BT + tx * 4;
+  MTileAcc A;
+  const f2 z2 = f2{0.f, 0.f};
+  A.L = A.sd = A.sdd = A.sdt = A.st = A.stt = z2;
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    const int lc0 = tx * 4 + ((2 * h) & 3) + ((2 * h) >> 2) * 64;
+    cx2[h] = f2{sc[1][lc0][0], sc[1][lc0 + 1][0]};
+    cy2[h] = f2{sc[1][lc0][1], sc[1][lc0 + 1][1]};
+    cz2[h] = f2{sc[1][lc0][2], sc[1][lc0 + 1][2]};
+    A.ax[h] = A.ay[h] = A.az[h] = A.bx[h] = A.by[h] = A.bz[h] = z2;
+  }
+  const bool interior = I != J && (I + 1) * BT <= N && (J + 1) * BT <= N;   // block-uniform
+  if (interior) {
+    mloss_rows<false, BG>(T, ldt, vec != 0, N, I, J, bg, sc, tx, ty, cx2, cy2, cz2, gj0, A, rowpart);
+    if constexpr (BG) {   // 64 pairs per thread, all at bg
+      const f2 sd = A.sd;
+      A.sdt = f2{bg * sd.x, bg * sd.y};
+      A.st = f2{32.f * bg, 32.f * bg};
+      A.stt = f2{32.f * bg * bg, 32.f * bg * bg};
+    }
+  } else {
+    mloss_rows<true, BG>(T, ldt, vec != 0, N, I, J, bg, sc, tx, ty, cx2, cy2, cz2, gj0, A, rowpart);
+  }
+
+  // column partials: reduce over the 4 ty of this wave (lanes l, l^16, l^32, l^48), then waves
+  const auto col_plane = [&](const f2 (&p)[4], int c) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float v = sum_rows4((q & 1) ? p[q >> 1].y : p[q >> 1].x);
+      const int lc = tx * 4 + (q & 3) + (q >> 2) * 64;
+      if (lane < 16) colred[c][wv][lc] = v;
+    }
+  };
+  col_plane(A.ax, 0);
+  col_plane(A.ay, 1);
+  col_plane(A.az, 2);
+  col_plane(A.bx, 3);
+  col_plane(A.by, 4);
+  col_plane(A.bz, 5);
+  {
+    double m[8] = {(double)A.L.x + (double)A.L.y,     (double)A.sd.x + (double)A.sd.y,
+                   (double)A.sdd.x + (double)A.sdd.y, (double)A.sdt.x + (double)A.sdt.y,
+                   (double)A.st.x + (double)A.st.y,   (double)A.stt.x + (double)A.stt.y,
+                   A.dg,                              A.sg};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      for (int o = 32; o > 0; o >>= 1) m[c] += shfl_xor_d(m[c], o);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) mred[wv][c] = m[c];
+    }
+  }
+  __syncthreads();
+  float4 *prow = part + (size_t)t * kMSlabs * BT;
+  if (tid < BT) {
+    float s[kMPlanes];
+#pragma unroll
+    for (int c = 0; c < kMPlanes; ++c) {
+      s[c] = colred[c][0][tid];
+#pragma unroll
+      for (int w2 = 1; w2 < 4; ++w2) s[c] += colred[c][w2][tid];
+    }
+    prow[BT + tid] = make_float4(s[0], s[1], s[2], 0.f);
+    prow[3 * BT + tid] = make_float4(s[3], s[4], s[5], 0.f);
+  } else {
+    const int lr = tid - BT;
+    float s[kMPlanes];
+#pragma unroll
+    for (int c = 0; c < kMPlanes; ++c) {
+      float v[16];
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const float4 o = *reinterpret_cast<const float4 *>(&rowpart[c * kRowPlane + lr * kRowPad + 4 * q4]);
+        v[4 * q4] = o.x; v[4 * q4 + 1] = o.y; v[4 * q4 + 2] = o.z; v[4 * q4 + 3] = o.w;
+      }
+      s[c] = v[0];
+#pragma unroll
+      for (int q = 1; q < 16; ++q) s[c] += v[q];   // tx order
+    }
+    prow[lr] = make_float4(s[0], s[1], s[2], 0.f);
+    prow[2 * BT + lr] = make_float4(s[3], s[4], s[5], 0.f);
+  }
+  if (tid < 8) mom[(size_t)t * 8 + tid] = ((mred[0][tid] + mred[1][tid]) + mred[2][tid]) + mred[3][tid];
+}
+
+// Second stage, one launch of 1024-thread blocks:
+//   blocks [0, row_blocks): R_i and W_i of 64 rows each -- the row slabs of tiles (R, J >= R) and the
+//     column slabs of tiles (J <= R, R), 16 J-groups added in group order, then corr[i] (the support
+//     pass's change of R_i, background form) -- into rw[i] (R) and rw[N + i] (W);
+//   blocks [row_blocks, row_blocks + kMomBlocks): runs of the moment records: components 0..6 over
+//     [0, m_all) (tiles, then the support pass's blocks), component 7 over the tiles only (the support
+//     pass's records have no such entry);
+//   the last block: sum_j c_j (x, y, z) and sum_i diag[i] (background form; else 0) in fp64 -> csum[4].
+// Every sum has a fixed order.
+__global__ __launch_bounds__(1024) void pairdist_mloss_reduce_kernel(const float4 *__restrict__ part, int N, int nb,
+                                                                     float4 *__restrict__ rw,
+                                                                     const double *__restrict__ mom, int64_t m_tiles,
+                                                                     int64_t m_all, int row_blocks,
+                                                                     double *__restrict__ mpart,
+                                                                     const float4 *__restrict__ corr,
+                                                                     const float *__restrict__ coords,
+                                                                     const float *__restrict__ diag,
+                                                                     double *__restrict__ csum) {
+  __shared__ __attribute__((aligned(16))) double shbuf[4 * 1024];   // 32 KB, one use per block kind
+  const int tid = threadIdx.x;
+  const int blk = blockIdx.x;
+  if (blk >= row_blocks + kMomBlocks) {   // coordinate and diagonal sums
+    double s[4] = {0, 0, 0, 0};
+    for (int j = tid; j < N; j += 1024) {
+      s[0] += (double)coords[3 * (size_t)j];
+      s[1] += (double)coords[3 * (size_t)j + 1];
+      s[2] += (double)coords[3 * (size_t)j + 2];
+      if (diag) s[3] += (double)diag[j];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) shbuf[c * 1024 + tid] = s[c];
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+      if (tid < o) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) shbuf[c * 1024 + tid] += shbuf[c * 1024 + tid + o];
+      }
+      __syncthreads();
+    }
+    if (tid < 4) csum[tid] = shbuf[tid * 1024];
+    return;
+  }
+  if (blk >= row_blocks) {   // moment partials
+    const int b = blk - row_blocks;
+    const int64_t per = (m_all + kMomBlocks - 1) / kMomBlocks;
+    const int64_t b0 = (int64_t)b * per, b1 = min(m_all, b0 + per);
+    if (tid < 256) {
+      double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (int64_t t = b0 + tid; t < b1; t += 256) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) s[c] += mom[(size_t)t * 8 + c];
+        if (t < m_tiles) s[7] += mom[(size_t)t * 8 + 7];
+      }
+#pragma unroll
+      for (int c = 0; c < 8; ++c) shbuf[c * 256 + tid] = s[c];
+    }
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) shbuf[c * 256 + tid] += shbuf[c * 256 + tid + o];
+      }
+      __syncthreads();
+    }
+    if (tid < 8) mpart[b * 8 + tid] = shbuf[tid * 256];
+    return;
+  }
+  float4 *red = reinterpret_cast<float4 *>(shbuf);   // [2][kRedGroups][64]
+  const int lr64 = tid & 63, grp = tid >> 6;
+  const int gi = blk * 64 + lr64;
+  float4 sr = make_float4(0.f, 0.f, 0.f, 0.f), sw = sr;
+  if (gi < N) {
+    const int R = gi / BT, lr = gi % BT;
+    const size_t st = (size_t)kMSlabs * BT;
+#pragma unroll 2
+    for (int J = grp; J < nb; J += kRedGroups) {
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a, d = a;
+      if (J >= R) {
+        const size_t trow = (size_t)(tri_start(R, nb) + (J - R));
+        a = part[trow * st + lr];
+        c = part[trow * st + 2 * BT + lr];
+      }
+      if (J <= R) {
+        const size_t tcol = (size_t)(tri_start(J, nb) + (R - J));
+        b = part[tcol * st + BT + lr];
+        d = part[tcol * st + 3 * BT + lr];
+      }
+      sr.x += a.x; sr.y += a.y; sr.z += a.z;
+      sr.x += b.x; sr.y += b.y; sr.z += b.z;
+      sw.x += c.x; sw.y += c.y; sw.z += c.z;
+      sw.x += d.x; sw.y += d.y; sw.z += d.z;
+    }
+  }
+  red[grp * 64 + lr64] = sr;
+  red[(kRedGroups + grp) * 64 + lr64] = sw;
+  __syncthreads();
+  if (grp == 0 && gi < N) {
+    float4 r0 = red[lr64], w0 = red[kRedGroups * 64 + lr64];
+#pragma unroll
+    for (int g = 1; g < kRedGroups; ++g) {
+      const float4 o = red[g * 64 + lr64], p = red[(kRedGroups + g) * 64 + lr64];
+      r0.x += o.x; r0.y += o.y; r0.z += o.z;
+      w0.x += p.x; w0.y += p.y; w0.z += p.z;
+    }
+    if (corr) {
+      const float4 o = corr[gi];
+      r0.x += o.x; r0.y += o.y; r0.z += o.z;
+    }
+    rw[gi] = r0;
+    rw[(size_t)N + gi] = w0;
+  }
+}
+
+// Finalize + combine, one launch.  Every block adds the kMomBlocks moment partials in block order
+// (the same bits in every block), forms mse, r, the loss value and the coefficients A, B, C of
+// g_ij = A d_ij + B t_ij + C in fp64, and then gives its 256 rows
+//   dcoords[i] = float(-B R_i + (A + B) (N c_i - sum_j c_j) + C W_i).
+// Block 0 writes stats[0..11] and loss.  stats: 0..6 the moments as hicgat_pairdist_mse_fused,
+// 7 mse, 8 pearson r (NaN when a variance is <= 0), 9 alpha (PEARSON) / 0 (RMSE) / mean of D - T over
+// all entries (SI_MSE), 10 the loss value, 11 sum_i T_ii.
+__global__ __launch_bounds__(256) void pairdist_mloss_finalize_kernel(const double *__restrict__ mpart,
+                                                                      const double *__restrict__ csum,
+                                                                      const float4 *__restrict__ rw,
+                                                                      const float *__restrict__ coords, int N,
+                                                                      int kind, double alpha,
+                                                                      double *__restrict__ stats,
+                                                                      float *__restrict__ loss,
+                                                                      float *__restrict__ dcoords) {
+  __shared__ double sm[8];
+  __shared__ double coef[3];
+  const int tid = threadIdx.x;
+  if (tid < 8) {
+    double s = 0.0;
+    for (int b = 0; b < kMomBlocks; ++b) s += mpart[b * 8 + tid];
+    sm[tid] = s;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const double n2 = (double)N * (double)N, M = 0.5 * (double)N * (double)(N - 1);
+    const double s0 = sm[0], sd = sm[1], sdd = sm[2], sdt = sm[3], st = sm[4], stt = sm[5], dg = sm[6];
+    const double sdiag = sm[7] + csum[3];
+    const double mse = (2.0 * s0 + dg) / n2;
+    double r = NAN, vd = 0.0, vt = 0.0;
+    if (M > 0.0) {
+      vd = sdd - sd * sd / M;
+      vt = stt - st * st / M;
+      // the tile sums are fp32 per thread: a variance below 2^-20 of the mean square is their rounding
+      // (N = 2: fl(d^2) - d^2), not a spread, and counts as <= 0
+      if (vd > kVarFloor * sdd && vt > kVarFloor * stt) r = (sdt - sd * st / M) / sqrt(vd * vt);
+    }
+    const double g4 = 4.0 / n2;
+    const double rmse = sqrt(mse + 1e-12);
+    const double ebar = (2.0 * (sd - st) - sdiag) / n2;   // the all-entries mean of D - T
+    // g_ij = A d_ij + B t_ij + C: the MSE part (halved by the root for RMSE), then the kind's own terms
+    const double base = kind == MLOSS_RMSE ? g4 / (2.0 * rmse) : g4;
+    double ea = 0.0, eb = 0.0, c = 0.0;
+    const bool pearson = kind == MLOSS_PEARSON && r == r;   // a variance <= 0: no gradient through the term
+    if (pearson) {
+      const double isq = 1.0 / sqrt(vd * vt);
+      ea = alpha * r / vd;
+      eb = alpha * isq;
+      c = alpha * ((st / M) * isq - r * (sd / M) / vd);
+    }
+    if (kind == MLOSS_SI_MSE) c = -g4 * ebar;
+    const double a = base + ea, b = -(base + eb);
+    double total, s9;
+    if (kind == MLOSS_PEARSON) {
+      total = mse + alpha * (pearson ? 1.0 - r : 1.0);   // r taken as 0 when it is undefined
+      s9 = alpha;
+    } else if (kind == MLOSS_RMSE) {
+      total = rmse;
+      s9 = 0.0;
+    } else {
+      total = mse - ebar * ebar;
+      s9 = ebar;
+    }
+    coef[0] = a;
+    coef[1] = b;
+    coef[2] = c;
+    if (blockIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) stats[k] = sm[k];
+      stats[7] = mse;
+      stats[8] = r;
+      stats[9] = s9;
+      stats[10] = total;
+      stats[11] = sdiag;
+      if (loss) loss[0] = (float)total;
+    }
+  }
+  __syncthreads();
+  const int i = blockIdx.x * 256 + tid;
+  if (dcoords && i < N) {
+    const double a = coef[0], b = coef[1], c = coef[2];
+    const float4 R = rw[i], W = rw[(size_t)N + i];
+    const double nn = (double)N;
+    const double ux = nn * (double)coords[3 * (size_t)i] - csum[0];
+    const double uy = nn * (double)coords[3 * (size_t)i + 1] - csum[1];
+    const double uz = nn * (double)coords[3 * (size_t)i + 2] - csum[2];
+    dcoords[3 * (size_t)i] = (float)(-b * (double)R.x + (a + b) * ux + c * (double)W.x);
+    dcoords[3 * (size_t)i + 1] = (float)(-b * (double)R.y + (a + b) * uy + c * (double)W.y);
+    dcoords[3 * (size_t)i + 2] = (float)(-b * (double)R.z + (a + b) * uz + c * (double)W.z);
+  }
+}
+
 }  // namespace hicgat
 
 using namespace hicgat;
@@ -1083,4 +1524,88 @@ extern "C" int hicgat_pairdist_mse_fused_support(const float *coords, const int3
     HICGAT_CHECK_LAUNCH();
   }
   return HICGAT_OK;
+}
+
+// ---- moment-dependent losses: tile pass -> reduce -> finalize + combine ---------------------------
+// workspace: [tiles][4][128] float4 slabs | (tiles + support blocks) moment records | kMomBlocks
+// partials | csum[4] | rw [2][N] float4 | corr [N] float4 | coordinates [N] float4 (the last two:
+// background form)
+static size_t mloss_workspace(int N, bool support) {
+  if (N <= 0) return 256;
+  const int64_t tiles = hicgat_pairdist_num_tiles(N, HICGAT_PD_TRI);
+  size_t b = (size_t)tiles * kMSlabs * BT * sizeof(float4) +
+             (size_t)(tiles + (support ? pd_support_blocks(N) : 0)) * 8 * sizeof(double) +
+             kMomBlocks * 8 * sizeof(double) + 4 * sizeof(double) + 2 * (size_t)N * sizeof(float4);
+  if (support) b += 2 * (size_t)N * sizeof(float4);
+  return b + 256;
+}
+
+extern "C" size_t hicgat_pairdist_moment_loss_workspace_bytes(int N) { return mloss_workspace(N, false); }
+extern "C" size_t hicgat_pairdist_moment_loss_support_workspace_bytes(int N) { return mloss_workspace(N, true); }
+
+// T == NULL: the background form (rowptr / col / val / diag and background)
+static int mloss_run(const float *coords, const float *T, int64_t ldt, int N, float background, const int32_t *rowptr,
+                     const int32_t *col, const float *val, const float *diag, int mloss_kind, double alpha,
+                     double *stats, float *loss, float *dcoords, void *workspace, hipStream_t s) {
+  const bool support = T == nullptr;
+  const int nb = pd_nb(N);
+  const int64_t tiles = (int64_t)nb * (nb + 1) / 2;
+  const int64_t sblocks = support ? pd_support_blocks(N) : 0;
+  char *p = static_cast<char *>(workspace);
+  float4 *part = reinterpret_cast<float4 *>(p);
+  double *mom = reinterpret_cast<double *>(p + (size_t)tiles * kMSlabs * BT * sizeof(float4));
+  double *mpart = mom + (size_t)(tiles + sblocks) * 8;
+  double *csum = mpart + kMomBlocks * 8;
+  float4 *rw = reinterpret_cast<float4 *>(csum + 4);
+  float4 *corr = support ? rw + 2 * (size_t)N : nullptr;
+  float4 *cpad = support ? corr + N : nullptr;
+  if (support) {
+    hipLaunchKernelGGL(pairdist_mloss_tile_kernel<true>, dim3(tiles), dim3(256), 0, s, coords, nullptr, N,
+                       (int64_t)0, 0, nb, part, mom, background, cpad);
+    HICGAT_CHECK_LAUNCH();
+    // the support's change of R_i and of sum (d-t)^2, sum dt, sum t, sum t^2, and sum T_ii^2: the combined
+    // loss's support pass as it is (W has no t in it: the bulk pass alone gives it)
+    hipLaunchKernelGGL(pairdist_support_kernel<KIND_COMBINED>, dim3(sblocks), dim3(256), 0, s, coords, N, background,
+                       0, N, rowptr, col, val, diag, corr, mom + (size_t)tiles * 8, nullptr, cpad);
+  } else {
+    const bool vec = (ldt % 4 == 0) && ((reinterpret_cast<uintptr_t>(T) & 15) == 0) && ldt >= (int64_t)nb * BT;
+    hipLaunchKernelGGL(pairdist_mloss_tile_kernel<false>, dim3(tiles), dim3(256), 0, s, coords, T, N, ldt,
+                       vec ? 1 : 0, nb, part, mom, 0.f, nullptr);
+  }
+  HICGAT_CHECK_LAUNCH();
+  const int row_blocks = (N + 63) / 64;
+  hipLaunchKernelGGL(pairdist_mloss_reduce_kernel, dim3(row_blocks + kMomBlocks + 1), dim3(1024), 0, s, part, N, nb,
+                     rw, mom, tiles, tiles + sblocks, row_blocks, mpart, corr, coords, support ? diag : nullptr,
+                     csum);
+  HICGAT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pairdist_mloss_finalize_kernel, dim3((N + 255) / 256), dim3(256), 0, s, mpart, csum, rw, coords,
+                     N, mloss_kind, alpha, stats, loss, dcoords);
+  HICGAT_CHECK_LAUNCH();
+  return HICGAT_OK;
+}
+
+static bool mloss_kind_ok(int k) { return k == MLOSS_PEARSON || k == MLOSS_RMSE || k == MLOSS_SI_MSE; }
+
+extern "C" int hicgat_pairdist_moment_loss(const float *coords, const float *T, int N, int64_t ldt, int mloss_kind,
+                                           double alpha, double *stats, float *loss, float *dcoords,
+                                           void *workspace, size_t workspace_bytes, hicgat_stream_t stream) {
+  if (N < 0 || !mloss_kind_ok(mloss_kind) || !(alpha == alpha)) return HICGAT_EINVAL;
+  if (N == 0) return HICGAT_OK;
+  if (!coords || !T || !stats || !workspace || ldt < N) return HICGAT_EINVAL;
+  if (workspace_bytes < mloss_workspace(N, false)) return HICGAT_EINVAL;
+  return mloss_run(coords, T, ldt, N, 0.f, nullptr, nullptr, nullptr, nullptr, mloss_kind, alpha, stats, loss,
+                   dcoords, workspace, (hipStream_t)stream);
+}
+
+extern "C" int hicgat_pairdist_moment_loss_support(const float *coords, int N, float background,
+                                                   const int32_t *rowptr, const int32_t *col, const float *val,
+                                                   const float *diag, int mloss_kind, double alpha, double *stats,
+                                                   float *loss, float *dcoords, void *workspace,
+                                                   size_t workspace_bytes, hicgat_stream_t stream) {
+  if (N < 0 || !mloss_kind_ok(mloss_kind) || !(alpha == alpha)) return HICGAT_EINVAL;
+  if (N == 0) return HICGAT_OK;
+  if (!coords || !rowptr || !col || !val || !diag || !stats || !workspace) return HICGAT_EINVAL;
+  if (workspace_bytes < mloss_workspace(N, true)) return HICGAT_EINVAL;
+  return mloss_run(coords, nullptr, 0, N, background, rowptr, col, val, diag, mloss_kind, alpha, stats, loss, dcoords,
+                   workspace, (hipStream_t)stream);
 }

@@ -24,6 +24,9 @@ Drop-in surface of the reference (beyzoskaya/HiC-GNN):
   hicgat.ops.bn_act_dropout                   ~ torch.nn.BatchNorm1d -> F.leaky_relu -> torch.nn.Dropout(p)
   hicgat.ops.act_dropout, hicgat.DropoutState ~ x.relu() / F.leaky_relu(x) -> torch.nn.Dropout(p)
   hicgat.ops.attention_dropout_mask           ~ the keep mask of GATConv(dropout=p) (tests, tools)
+  hicgat.ops.fused_dist_loss(kind="mse+pearson" | "rmse" | "si_mse", alpha=...)
+                                              ~ mse_loss + alpha * (1 - r) with a gradient through r, rmse_loss,
+                                                scale_invariant_mse (HiC_GAT_generalize_directly.py:60-68, :219-225)
   hicgat.graph.load_input / cont2dist / convert_to_matrix / Adj
                                               ~ utils.py:10-80 (+ torch_sparse.SparseTensor)
   hicgat.train.train / main                   ~ HiC-GNN_main.py:107-160

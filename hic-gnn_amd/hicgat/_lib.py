@@ -89,6 +89,11 @@ SIGNATURES = {
     "hicgat_pairdist_mse_fused_support": (c_int, [c_p, c_p, c_int, c_f, c_p, c_p, c_p, c_p, c_i64, c_i64,
                                                   c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "hicgat_pairdist_support_workspace_bytes": (c_sz, [c_int]),
+    "hicgat_pairdist_moment_loss": (c_int, [c_p, c_p, c_int, c_i64, c_int, c_d, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "hicgat_pairdist_moment_loss_support": (c_int, [c_p, c_int, c_f, c_p, c_p, c_p, c_p, c_int, c_d, c_p, c_p,
+                                                    c_p, c_p, c_sz, c_p]),
+    "hicgat_pairdist_moment_loss_workspace_bytes": (c_sz, [c_int]),
+    "hicgat_pairdist_moment_loss_support_workspace_bytes": (c_sz, [c_int]),
     "hicgat_xagg_vec_bytes": (c_sz, []),
     "hicgat_xagg_logits": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
                                    c_i64, c_p, c_p, c_p, c_p, c_sz, c_p]),

@@ -376,6 +376,10 @@ class SimComm:
 
 class ShardedTrainer:
     def __init__(self, model, x, adj, truth, lr=1e-3, kind="mse", group=None, kern=None, mode="auto", comm=None):
+        if kind in ops.MOMENT_LOSS_KINDS:
+            # before any collective or launch: these losses have no tile-range / band form
+            raise NotImplementedError(f"ShardedTrainer does not run loss {kind!r}: the moment-dependent losses "
+                                      f"({', '.join(ops.MOMENT_LOSS_KINDS)}) are single-GPU hicgat.train only")
         if any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in model.modules()):
             # before any collective (and before the conv check, so both BatchNorm models say why): batch
             # statistics over sharded rows would need a collective of their own

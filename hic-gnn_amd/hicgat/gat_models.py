@@ -74,10 +74,10 @@ class _CoordsModel(torch.nn.Module):
     def forward(self, x, edge_index):
         return ops.pairwise_dist(self.get_model(x, edge_index))
 
-    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None):
+    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None, alpha=1.0):
         """Fused ``criterion(model(x, ei), truth)``; returns ``(loss, stats, coords)``."""
         coords = self.get_model(x, edge_index)
-        loss, stats = ops.fused_dist_loss(coords, truth, kind, tile_range, stats)
+        loss, stats = ops.fused_dist_loss(coords, truth, kind, tile_range, stats, alpha)
         return loss, stats, coords
 
 
@@ -219,9 +219,9 @@ class GATNetHeadsChanged3LayersEmbeddingDim256Entropy(_CoordsModel):
         coords, attn = self.coords_and_attention(x, edge_index)
         return ops.pairwise_dist(coords), attn
 
-    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None):
+    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None, alpha=1.0):
         coords, attn = self.coords_and_attention(x, edge_index)
-        loss, stats = ops.fused_dist_loss(coords, truth, kind, tile_range, stats)
+        loss, stats = ops.fused_dist_loss(coords, truth, kind, tile_range, stats, alpha)
         w = attn.storage.value()
         loss = loss + (self.alpha / (x.shape[0] * w.shape[1])) * ops.attention_entropy(w)
         return loss, stats, coords
@@ -264,9 +264,9 @@ class GATNetReduced(_CoordsModel):
         self._no_training()
         return super().forward(x, edge_index)
 
-    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None):
+    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None, alpha=1.0):
         self._no_training()
-        return super().loss(x, edge_index, truth, kind, tile_range, stats)
+        return super().loss(x, edge_index, truth, kind, tile_range, stats, alpha)
 
 
 class _DropoutMLP(_CoordsModel):
@@ -325,9 +325,9 @@ class _DropoutMLP(_CoordsModel):
     def forward(self, x, edge_index):
         return ops.pairwise_dist(self._coords(x, edge_index))
 
-    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None):
+    def loss(self, x, edge_index, truth, kind="mse", tile_range=(0, -1), stats=None, alpha=1.0):
         coords = self._coords(x, edge_index)
-        loss, stats = ops.fused_dist_loss(coords, truth, kind, tile_range, stats)
+        loss, stats = ops.fused_dist_loss(coords, truth, kind, tile_range, stats, alpha)
         return loss, stats, coords
 
 

@@ -413,6 +413,23 @@ class HipKernels:
                 int(t1), int(s0), int(s1), int(kind), P(stats), P(loss), P(d32), P(d64), P(ws), ws.numel(),
                 _lib.stream(coords.device)), "hicgat_pairdist_mse_fused_support")
 
+    def moment_loss(self, coords, tbuf, n, mkind, alpha, stats, loss, dcoords):
+        """A moment-dependent loss (``ops.MOMENT_LOSS_KINDS``) over the whole dense truth ``tbuf``."""
+        ws = _lib.workspace(self.lib.hicgat_pairdist_moment_loss_workspace_bytes(n), coords.device)
+        with _timed("pairdist_moment_loss"):
+            _lib.check(self.lib.hicgat_pairdist_moment_loss(
+                P(coords), P(tbuf), n, tbuf.shape[1], int(mkind), float(alpha), P(stats), P(loss), P(dcoords), P(ws),
+                ws.numel(), _lib.stream(coords.device)), "hicgat_pairdist_moment_loss")
+
+    def moment_loss_support(self, coords, sf, n, mkind, alpha, stats, loss, dcoords):
+        """The same over a truth in background + support form (``graph.SupportForm``)."""
+        ws = _lib.workspace(self.lib.hicgat_pairdist_moment_loss_support_workspace_bytes(n), coords.device)
+        with _timed("pairdist_moment_loss"):
+            _lib.check(self.lib.hicgat_pairdist_moment_loss_support(
+                P(coords), n, sf.background, P(sf.rowptr), P(sf.col_buf), P(sf.val_buf), P(sf.diag), int(mkind),
+                float(alpha), P(stats), P(loss), P(dcoords), P(ws), ws.numel(), _lib.stream(coords.device)),
+                "hicgat_pairdist_moment_loss_support")
+
     def loss_finalize(self, n, kind, stats, loss, dc64=None, r0=0, r1=0, dcoords=None, reorder=None):
         """mse / r / alpha / total from the (all-reduced) moments; with ``dc64`` also dcoords[r0:r1] =
         fp32(dc64[r0:r1]) in the same launch; ``reorder`` = (cbuf, gidx32, cglob): also cglob[i] =

@@ -1156,10 +1156,34 @@ def backward_from_loss(loss):
     torch.autograd.backward(loss, grad_tensors=seed)
 
 
+class _MomentLossFn(torch.autograd.Function):
+    """The moment-dependent losses: value and d(loss)/d(coords) from one chain of launches."""
+
+    @staticmethod
+    def forward(ctx, coords, tbuf, n, mkind, alpha, stats, support=None):
+        c = coords.contiguous().float()
+        dc = torch.empty_like(c)
+        loss = torch.empty((), dtype=torch.float32, device=c.device)
+        if support is not None:
+            kernels.default().moment_loss_support(c, support, n, mkind, alpha, stats, loss, dc)
+        else:
+            kernels.default().moment_loss(c, tbuf, n, mkind, alpha, stats, loss, dc)
+        ctx.save_for_backward(dc)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        (dc,) = ctx.saved_tensors
+        if gl is _UNIT_SEEDS.get(gl.device) and gl._version == 0:   # as _FusedLossFn
+            return dc, None, None, None, None, None, None
+        return dc * gl, None, None, None, None, None, None
+
+
 LOSS_KINDS = {"mse": 0, "combined": 1, "contrastive": 2}   # include/hicgat.h loss_kind
+MOMENT_LOSS_KINDS = {"mse+pearson": 0, "rmse": 1, "si_mse": 2}   # include/hicgat.h mloss_kind
 
 
-def fused_dist_loss(coords, truth, kind="mse", tile_range=(0, -1), stats=None):
+def fused_dist_loss(coords, truth, kind="mse", tile_range=(0, -1), stats=None, alpha=1.0):
     """MSE(cdist(coords), truth) [kind="mse", HiC-GNN_main.py:127],
     MSE + alpha*(1 - pearson) [kind="combined", HiC_GAT_generalize_directly.py:219-225] with the
     gradient of the MSE only (the Pearson term is a detached host value in the reference), or
@@ -1169,11 +1193,26 @@ def fused_dist_loss(coords, truth, kind="mse", tile_range=(0, -1), stats=None):
     ``truth`` is a ``graph.Truth`` (stored symmetric; an asymmetric target is folded into the
     equivalent symmetric form there); with a background + support form (``truth.support``, e.g.
     cont2dist's target) the whole-matrix loss reads no truth in its O(N^2) pass.  ``stats`` (float64 [12], device) receives the moments, mse,
-    r, alpha and total (see include/hicgat.h)."""
+    r, alpha and total (see include/hicgat.h).
+
+    The kinds of ``MOMENT_LOSS_KINDS`` are differentiable through the global moments of D and T:
+    ``"mse+pearson"`` = mse + ``alpha`` * (1 - r) with the gradient through both terms (``alpha`` a
+    fixed weight, not the reference's dynamic one), ``"rmse"`` = sqrt(mse + 1e-12) and ``"si_mse"`` =
+    mean((e - mean e)^2), e = D - T over all N^2 entries (HiC_GAT_generalize_directly.py:60-68).  Still
+    one O(N^2) pass; whole matrix only (no ``tile_range``), and a symmetric truth only."""
+    if kind in MOMENT_LOSS_KINDS and truth.asymmetric_source:
+        # the symmetric fold keeps the MSE and its gradient only, not the t-moments of these losses
+        raise ValueError(f"loss {kind!r} needs a symmetric truth; this one was folded from an asymmetric target")
     _lib.lib()
     _dev_check(coords)
     if stats is None:
         stats = torch.empty(12, dtype=torch.float64, device=coords.device)
+    if kind in MOMENT_LOSS_KINDS:
+        if (int(tile_range[0]), int(tile_range[1])) not in ((0, -1), (0, kernels.default().num_tiles(truth.n))):
+            raise ValueError(f"loss {kind!r} runs over the whole matrix only (tile_range {tuple(tile_range)})")
+        loss = _MomentLossFn.apply(coords, truth.buf, truth.n, MOMENT_LOSS_KINDS[kind], float(alpha), stats,
+                                   getattr(truth, "support", None))
+        return loss, stats
     kind_i = LOSS_KINDS[kind]
     if kind == "contrastive":
         truth = truth.upper()       # the contrastive loss reads truth[triu] as given

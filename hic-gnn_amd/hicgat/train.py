@@ -24,7 +24,7 @@ from .gat_models import ALL_MODELS, MODELS, model_class  # noqa: F401
 from .optim import FlatAdam
 
 
-def train_step(model, opt, x, edge_index, truth, kind="mse", stats=None):
+def train_step(model, opt, x, edge_index, truth, kind="mse", stats=None, alpha=1.0):
     """One step without any host sync: returns (loss tensor, stats tensor, coords)."""
     model.train()
     pk = ops.step_pack(model, x) if x.is_cuda else None   # the tail's packed weights ride in the first launch
@@ -33,7 +33,10 @@ def train_step(model, opt, x, edge_index, truth, kind="mse", stats=None):
     else:
         opt.zero_grad()
     with ops.prepacked(model, pk):
-        loss, stats, coords = model.loss(x, edge_index, truth, kind, stats=stats)
+        if kind in ops.MOMENT_LOSS_KINDS:
+            loss, stats, coords = model.loss(x, edge_index, truth, kind, stats=stats, alpha=alpha)
+        else:
+            loss, stats, coords = model.loss(x, edge_index, truth, kind, stats=stats)
     with ops.overlapped_param_grads(None if x.is_cuda else False):   # dW, db beside the backward
         ops.backward_from_loss(loss)
     opt.step()
@@ -43,7 +46,7 @@ def train_step(model, opt, x, edge_index, truth, kind="mse", stats=None):
 GRAPH_WARMUP = 2   # eager steps before the step is captured (real training steps, in the history)
 
 
-LOSSES = ("mse", "combined", "contrastive", "mse+dscc")
+LOSSES = ("mse", "combined", "contrastive", "mse+dscc", "mse+pearson", "rmse", "si_mse")
 
 
 def train(model, data, truth, lr=1e-3, thresh=1e-8, steps=None, loss="mse", max_steps=1_000_000,
@@ -66,6 +69,10 @@ def train(model, data, truth, lr=1e-3, thresh=1e-8, steps=None, loss="mse", max_
     (:132-133: the step's own for a model without dropout sites, a second no-grad forward for a
     ``_DropoutMLP``); fixed ``steps`` gives the script's epoch loop.  ``dscc_history`` then receives
     each step's rho and ``mse_history`` (a list) the MSE part.
+
+    ``loss="mse+pearson"`` (mse + ``alpha`` * (1 - r), the gradient through both terms), ``"rmse"`` and
+    ``"si_mse"`` are the moment-dependent kinds of ``ops.fused_dist_loss``; the recorded value is the fp32
+    loss and ``dscc_history`` works as for ``"mse"``.
 
     ``attn_dropout`` = p > 0 sets ``model.conv.dropout`` (PyG's GATConv(dropout=p): dropout on the
     attention coefficients in training mode; 0 leaves the model as it is).  The conv's own
@@ -98,7 +105,7 @@ def train(model, data, truth, lr=1e-3, thresh=1e-8, steps=None, loss="mse", max_
         if rescore:      # :132 get_model never drops; run on this step's parameters, before their update
             with torch.no_grad():
                 scored = model.get_model(data.x, data.edge_index).contiguous()
-        val, st, coords = train_step(model, opt, data.x, data.edge_index, truth, kind, stats)
+        val, st, coords = train_step(model, opt, data.x, data.edge_index, truth, kind, stats, alpha)
         if scorer is not None:
             host[4].copy_(st[10] if kind == "contrastive" else val.detach())
             scorer.score_into(coords.detach().contiguous() if scored is None else scored, host)
@@ -168,7 +175,8 @@ def make_parser():
     p.add_argument("--model", default="GATNetSelectiveResidualsUpdated", choices=sorted(ALL_MODELS))
     p.add_argument("--loss", default="mse", choices=list(LOSSES))
     p.add_argument("--alpha", type=float, default=1.0, help="weight of the (1 - dSCC) term of --loss mse+dscc "
-                                                            "(combined_loss_training.py:142)")
+                                                            "(combined_loss_training.py:142) or of the (1 - r) "
+                                                            "term of --loss mse+pearson")
     p.add_argument("--attn-dropout", type=float, default=0.0, metavar="P",
                    help="dropout on the GATConv's attention coefficients while training (PyG's "
                         "GATConv(dropout=P)); 0: none")
@@ -215,7 +223,7 @@ def main(argv=None):
     for f in conv:
         print(f"Training model using conversion value {f}.")
         model = model_class(a.model)().to(data.x.device)
-        extra = {"alpha": a.alpha} if a.loss == "mse+dscc" else {}
+        extra = {"alpha": a.alpha} if a.loss in ("mse+dscc", "mse+pearson") else {}
         if a.attn_dropout:
             extra["attn_dropout"] = a.attn_dropout
         _, hist = train(model, data, truth, a.learningrate, a.threshold, a.steps, a.loss, **extra)

@@ -401,6 +401,39 @@ int hicgat_pairdist_mse_fused_support(const float *coords, const int32_t *cmap, 
                                       double *stats, float *loss, float *dcoords, double *dcoords64,
                                       void *workspace, size_t workspace_bytes, hicgat_stream_t stream);
 size_t hicgat_pairdist_support_workspace_bytes(int N);
+/* ---- moment-dependent distance losses: the gradient weight of a pair depends on the global moments ----
+ * mloss_kind (T symmetric, M = N(N-1)/2 pairs i < j, "all entries" = the N^2 entries with D_ii = 0):
+ *   HICGAT_MLOSS_PEARSON: mse + alpha * (1 - r), mse the all-entries mean of (D - T)^2, r Pearson over
+ *     the pairs, alpha the caller's fixed weight; the gradient goes through both terms.  A variance
+ *     <= 0 (collapsed coordinates, constant truth): r taken as 0 in the value (combined_loss_training.py:
+ *     136-138), no gradient from the term, stats[8] stays NaN;
+ *   HICGAT_MLOSS_RMSE:    sqrt(mse + 1e-12) (HiC_GAT_generalize_directly.py:60-62);
+ *   HICGAT_MLOSS_SI_MSE:  the all-entries mean of (e - ebar)^2, e = D - T, ebar its all-entries mean
+ *     (scale_invariant_mse, HiC_GAT_generalize_directly.py:64-68).
+ * Each derivative per pair is A d_ij + B t_ij + C with A, B, C functions of the moments, so ONE tile
+ * pass accumulates R_i = sum_j (d_ij - t_ij) u_ij and W_i = sum_j u_ij, u_ij = (c_i - c_j)/d_ij (0 where
+ * d_ij = 0), a second kernel reduces them per row, and a third finalizes the moments, forms A, B, C in
+ * fp64 on the device and writes dcoords[i] = float(-B R_i + (A + B)(N c_i - sum_j c_j) + C W_i).  No
+ * host read; the three launches (four in the background form) can be captured in a graph.  Whole
+ * matrix only (no tile range, band or cmap).  alpha is read by HICGAT_MLOSS_PEARSON only.  Outputs:
+ *   stats[12] (float64): 0..6 the moments as hicgat_pairdist_mse_fused (all seven, every kind), 7 mse,
+ *     8 pearson r (NaN when a variance is <= 0), 9 alpha (PEARSON) / 0 (RMSE) / ebar (SI_MSE), 10 the
+ *     loss value, 11 sum_i T_ii;
+ *   loss[1] (float32, may be NULL): float(stats[10]);  dcoords [N,3] (may be NULL): d(loss)/dcoords.
+ * T: the whole truth, element (i, j) at T[i * ldt + j], ldt >= N.  The _support form takes the truth
+ * in background form, as hicgat_pairdist_mse_fused_support does (W comes from the bulk pass alone; R
+ * and the t-moments take the support pass's correction).
+ * workspace: hicgat_pairdist_moment_loss_workspace_bytes(N) / ..._support_workspace_bytes(N). */
+enum { HICGAT_MLOSS_PEARSON = 0, HICGAT_MLOSS_RMSE = 1, HICGAT_MLOSS_SI_MSE = 2 };
+int hicgat_pairdist_moment_loss(const float *coords, const float *T, int N, int64_t ldt, int mloss_kind,
+                                double alpha, double *stats, float *loss, float *dcoords, void *workspace,
+                                size_t workspace_bytes, hicgat_stream_t stream);
+int hicgat_pairdist_moment_loss_support(const float *coords, int N, float background, const int32_t *rowptr,
+                                        const int32_t *col, const float *val, const float *diag, int mloss_kind,
+                                        double alpha, double *stats, float *loss, float *dcoords, void *workspace,
+                                        size_t workspace_bytes, hicgat_stream_t stream);
+size_t hicgat_pairdist_moment_loss_workspace_bytes(int N);
+size_t hicgat_pairdist_moment_loss_support_workspace_bytes(int N);
 /* The background form of a symmetric N x N fp32 truth T (leading dim ldt): the sorted CSR of the
  * off-diagonal entries != background, their values, and the diagonal.  Two calls, as
  * hicgat_csr_from_dense: col == NULL fills rowptr (the counts, scanned); then col / val / diag. */
