@@ -15,6 +15,10 @@
 // become one GEMM against [W_l | W_r] (K = 2F).  One wave per row gathers 2 KiB x rows with the
 // neighbour id and its weight broadcast through SGPRs; the transposed product (d agg -> d x) uses
 // the CSR symmetry: row j's entries are the (i, j) edges, weighted by inv_deg of the neighbour.
+//
+// Features must be finite.  sage_agg_f512_kernel multiplies the self-loop entry and the lanes past the
+// end of a row's last 4-group by p = 0 (they read x[i]), where sage_agg_generic_kernel skips them: an
+// inf or NaN in x[i] would reach agg_i as 0 * inf = NaN on the fast path only.
 #include "common.hpp"
 
 namespace hicgat {
