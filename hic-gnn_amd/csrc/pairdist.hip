@@ -12,8 +12,14 @@
 // w*(c_i - c_j) into row partials (reduced over the 16 tx lanes) and column partials (reduced over
 // ty through LDS).  Partials go to a [tile][2][128] float4 slab and a second kernel adds, per row,
 // the slabs of every tile touching it in a fixed order: bitwise reproducible, no float atomics.
+//
+// Two chains share everything around the per-pair arithmetic (stage_coords, col_partials / col_sums /
+// row_sums, the moment records, gather_row, moments_partial_block, moment_stats, PdLayout): the
+// fixed-weight chain (MSE, combined, contrastive: 3 float planes, 7 moments, 2 slabs per tile) and the
+// moment-dependent chain (mloss: 6 planes, 8 moments, 4 slabs per tile).
 #include <algorithm>
 #include <type_traits>
+#include <cstdint>
 #include <cstdlib>
 
 #include "common.hpp"
@@ -75,6 +81,30 @@ __device__ __forceinline__ double shfl_xor_d(double v, int m) {
   return *reinterpret_cast<double *>(&q);
 }
 
+__device__ __forceinline__ void add3(float4 &s, const float4 &o) { s.x += o.x; s.y += o.y; s.z += o.z; }
+
+// A 256-thread block's moment record, M doubles: the components of MASK summed over the wave (the
+// others are taken from lane 0 as they are: the callers leave those at 0) into mred[wave]; after a
+// barrier, moment_record adds the 4 waves in the fixed order ((0 + 1) + 2) + 3.
+template <int M, unsigned MASK = (1u << M) - 1>
+__device__ __forceinline__ void moment_wave_sums(double (&m)[M], double (*mred)[M], int lane, int wv) {
+#pragma unroll
+  for (int c = 0; c < M; ++c) {
+    if (!((MASK >> c) & 1)) continue;
+    for (int o = 32; o > 0; o >>= 1) m[c] += shfl_xor_d(m[c], o);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < M; ++c) mred[wv][c] = m[c];
+  }
+}
+
+template <int M>
+__device__ __forceinline__ void moment_record(const double (*mred)[M], double *__restrict__ rec) {
+  const int c = threadIdx.x;
+  if (c < M) rec[c] = ((mred[0][c] + mred[1][c]) + mred[2][c]) + mred[3][c];
+}
+
 // Row partials of the background form: each thread's 8-column partial of every row it touches goes
 // to LDS and threads 128..255 add the 16 per row in tx order at the end, while 0..127 add the column
 // partials -- instead of three 16-lane DPP sums per row inside the pair loop (~20 % of its VALU
@@ -84,6 +114,8 @@ __device__ __forceinline__ double shfl_xor_d(double v, int m) {
 // sums read their 16 floats as four conflict-free ds_read_b128 (80-B rows: 16 lanes, 16 slots).
 constexpr int kRowPad = 20;
 constexpr int kRowPlane = BT * kRowPad;
+
+// ---- per-pair bodies ------------------------------------------------------------------------------
 
 // Per-thread accumulators of one tile: the moments and the column partials of its 8 columns.
 struct TileAcc {
@@ -301,501 +333,6 @@ __device__ __forceinline__ void tile_rows_pk(const float *tile, float bg, const 
   }
 }
 
-
-// MODE_SYM: T = symmetric truth, tiles I <= J, pairs i < j, w = (d - t)/d (scale 4/N^2 later).
-// MODE_FULL: T = upstream grad G of D, all tiles, pairs i != j, w = g/d.
-// KIND: KIND_MSE: sum (d - t)^2; KIND_COMBINED: also the d / t moments of the Pearson term;
-// KIND_CONTRASTIVE: sum |d - t| and w = sgn(d - t) / d.
-// BG: the background form (T = bg at every pair; no T read, no diagonal term -- the support pass,
-// pairdist_support_kernel, adds the entries that differ and the diagonal).
-template <int KIND>
-__device__ void support_block(const float *__restrict__ coords, float bg, int row_begin, int row_end,
-                              const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                              const float *__restrict__ val, const float *__restrict__ diag, float4 *__restrict__ corr,
-                              double *__restrict__ mom, const int *__restrict__ cmap, int blk,
-                              const float4 *__restrict__ cpad = nullptr);
-
-// The support pass riding in the background-form tile launch (SUP): blocks [ntiles, ntiles +
-// blocks) of the grid run pairdist_support_kernel's work for support block (blockIdx.x - ntiles).
-struct SupportArgs {
-  const int32_t *rowptr = nullptr, *col = nullptr;
-  const float *val = nullptr, *diag = nullptr;
-  float4 *corr = nullptr;
-  double *mom = nullptr;
-  int row_begin = 0, row_end = 0;
-  int64_t ntiles = 0;
-};
-
-// The background form is latency-bound and is built for four workgroups per CU: <= 128 VGPRs (the
-// launch bound makes the compiler hold to them) and <= 40 KB of LDS; tests/test_pairdist_resources_host.py
-// checks both from the kernel metadata.
-template <int MODE, bool VEC, int KIND, bool BG = false, bool SUP = false>
-__global__ __launch_bounds__(256, BG ? 4 : 1) void pairdist_tile_kernel(const float *__restrict__ coords,
-                                                            const float *__restrict__ T, int N,
-                                                            int64_t ldt, int64_t row0, int64_t col0,
-                                                            int nb, int64_t t0,
-                                                            float4 *__restrict__ part,
-                                                            double *__restrict__ mom, float bg,
-                                                            const int *__restrict__ cmap = nullptr,
-                                                            const SupportArgs sup = SupportArgs{},
-                                                            float4 *__restrict__ cpad = nullptr) {
-  static_assert(!BG || (MODE == MODE_SYM && !VEC), "the background form is the training loss without a T image");
-  static_assert(!SUP || BG, "the support pass rides only in the background form's launch");
-  if (SUP && (int64_t)blockIdx.x >= sup.ntiles) {   // block-uniform
-    support_block<KIND>(coords, bg, sup.row_begin, sup.row_end, sup.rowptr, sup.col, sup.val, sup.diag, sup.corr,
-                           sup.mom, cmap, (int)(blockIdx.x - sup.ntiles));
-    return;
-  }
-  // one dynamic LDS array: [T tile 128x128 fp32 (VEC only)] -- 64 KiB, 16-B aligned
-  extern __shared__ __attribute__((aligned(16))) float tile[];
-  __shared__ float sc[2][BT][3];
-  __shared__ float colred[3][4][BT];   // planar x / y / z: [wave][column]
-  __shared__ double mred[4][7];
-  constexpr bool RL = BG;
-  __shared__ __attribute__((aligned(16))) float rowpart_s[RL ? 3 * kRowPlane : 1];
-  float *rowpart = RL ? rowpart_s : nullptr;
-  const int64_t t = t0 + blockIdx.x;
-  int I, J;
-  if (MODE == MODE_SYM) {
-    tri_decode(t, nb, I, J);
-  } else {
-    I = (int)(t / nb);
-    J = (int)(t % nb);
-  }
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lane = tid & 63, wv = tid >> 6;
-  for (int k = tid; k < 2 * BT; k += 256) {
-    const int which = k / BT, li = k % BT;
-    const int g = (which ? J : I) * BT + li;
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (g < N) {
-      const size_t gc = cmap ? (size_t)cmap[g] : (size_t)g;   // cmap: global row -> coords row (sharded step)
-      x = coords[3 * gc];
-      y = coords[3 * gc + 1];
-      z = coords[3 * gc + 2];
-    }
-    sc[which][li][0] = x;
-    sc[which][li][1] = y;
-    sc[which][li][2] = z;
-    // the diagonal tile of row block I writes its rows' float4 copy for the support pass that follows
-    if (cpad && I == J && which == 0 && g < N) cpad[g] = make_float4(x, y, z, 0.f);
-  }
-  if (VEC) {
-    // LDS-DMA of the T tile (global_load_lds_dwordx4: each wave instruction moves 1 KiB = two 512-B
-    // tile rows, wave-uniform LDS base + lane*16), each wave only the 32 rows its threads read:
-    // rows 16w .. 16w+15 (k = 0..3 of tile_rows) first, then 64+16w .. 64+16w+15 (k = 4..7), so the
-    // first half is computed while the second is in flight.  Rows past N are clamped to a valid row
-    // (their values are masked); columns past N lie inside the padded leading dimension.  T may be
-    // a band of the truth (rows from row0, columns from col0: a rank's share, hicgat.dist).
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int r0 = (q < 8 ? 0 : 64) + wv * 16 + (q & 7) * 2;
-      const int gi = min(I * BT + r0 + (lane >> 5), N - 1);
-      const float *src = T + (size_t)(gi - row0) * ldt + (size_t)((int64_t)J * BT - col0) + (lane & 31) * 4;
-      __builtin_amdgcn_global_load_lds(src, &tile[r0 * BT], 16, 0, 0);
-    }
-  }
-  // sc[] (written above with ds_write) to all waves: LDS drain + raw barrier -- __syncthreads()
-  // would also drain vmcnt and so wait for the whole tile
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  float cx[8], cy[8], cz[8];
-  const int gj0 = J * BT + tx * 4;
-  TileAcc A;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const int lc = tx * 4 + (q & 3) + (q >> 2) * 64;
-    cx[q] = sc[1][lc][0];
-    cy[q] = sc[1][lc][1];
-    cz[q] = sc[1][lc][2];
-    A.ax[q] = A.ay[q] = A.az[q] = 0.f;
-  }
-  float4 *prow = part + (size_t)t * 2 * BT;
-  const bool interior = I != J && (I + 1) * BT <= N && (J + 1) * BT <= N;   // block-uniform
-  if (VEC) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // this wave's first 16 rows landed
-  constexpr bool PK = (VEC || BG) && MODE == MODE_SYM;   // packed interior path (tile_rows_pk)
-  if constexpr (BG) {
-    // no T image to wait for between the halves: one branch around both, so the interior and the
-    // masked form never share a live range (the two half-calls stay: each half's moments are
-    // summed on their own and then added, the order the records have always had)
-    if (interior) {
-      tile_rows_pk<KIND, 0, 4, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
-      tile_rows_pk<KIND, 4, 8, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
-    } else {
-      tile_rows<MODE, VEC, KIND, true, 0, 4, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
-      tile_rows<MODE, VEC, KIND, true, 4, 8, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
-    }
-  } else {
-    if (interior) {
-      if constexpr (PK) tile_rows_pk<KIND, 0, 4, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
-      else tile_rows<MODE, VEC, KIND, false, 0, 4>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
-    } else {
-      tile_rows<MODE, VEC, KIND, true, 0, 4, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
-    }
-    if (VEC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // and the second 16
-    if (interior) {
-      if constexpr (PK) tile_rows_pk<KIND, 4, 8, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
-      else tile_rows<MODE, VEC, KIND, false, 4, 8>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
-    } else {
-      tile_rows<MODE, VEC, KIND, true, 4, 8, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
-    }
-  }
-
-  // column partials: reduce over the 4 ty of this wave (lanes l, l^16, l^32, l^48), then waves
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    A.ax[q] = sum_rows4(A.ax[q]);
-    A.ay[q] = sum_rows4(A.ay[q]);
-    A.az[q] = sum_rows4(A.az[q]);
-  }
-  if (lane < 16) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int lc = tx * 4 + (q & 3) + (q >> 2) * 64;
-      colred[0][wv][lc] = A.ax[q];
-      colred[1][wv][lc] = A.ay[q];
-      colred[2][wv][lc] = A.az[q];
-    }
-  }
-  if (MODE == MODE_SYM) {
-    constexpr bool PEARSON = KIND == KIND_COMBINED;
-    double m[7] = {A.L, A.sd, A.sdd, A.sdt, A.st, A.stt, A.dg};
-#pragma unroll
-    for (int c = 0; c < 7; ++c) {
-      if (!PEARSON && c >= 1 && c <= 5) continue;
-      for (int o = 32; o > 0; o >>= 1) m[c] += shfl_xor_d(m[c], o);
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int c = 0; c < 7; ++c) mred[wv][c] = m[c];
-    }
-  }
-  __syncthreads();
-  if (tid < BT) {
-    float s[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      s[c] = colred[c][0][tid];
-#pragma unroll
-      for (int w2 = 1; w2 < 4; ++w2) s[c] += colred[c][w2][tid];
-    }
-    prow[BT + tid] = make_float4(s[0], s[1], s[2], 0.f);
-  } else if (RL) {
-    const int lr = tid - BT;
-    float s[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float v[16];
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 o = *reinterpret_cast<const float4 *>(&rowpart[c * kRowPlane + lr * kRowPad + 4 * q4]);
-        v[4 * q4] = o.x; v[4 * q4 + 1] = o.y; v[4 * q4 + 2] = o.z; v[4 * q4 + 3] = o.w;
-      }
-      s[c] = v[0];
-#pragma unroll
-      for (int q = 1; q < 16; ++q) s[c] += v[q];   // tx order, as the 16 entries were always added
-    }
-    prow[lr] = make_float4(s[0], s[1], s[2], 0.f);
-  }
-  if (MODE == MODE_SYM && tid < 7) {
-    mom[(size_t)t * 8 + tid] = ((mred[0][tid] + mred[1][tid]) + mred[2][tid]) + mred[3][tid];
-  }
-}
-
-// dcoords[i] = scale * (sum of the row partials of tiles (R, *) + column partials of (*, R));
-// ncol = column slabs per tile (1 here; the slab layout is [row partials | ncol column partials]).
-// Block = 64 rows x 4 groups; group g adds the tiles J = g, g+4, ... of its row, then the 4 group
-// sums are combined in group order (fixed order: bitwise reproducible).
-constexpr int kRedGroups = 16;   // J-groups per row in pairdist_reduce (1024-thread blocks)
-
-__device__ void moments_partial_block(const double *__restrict__ mom, int64_t t0, int64_t t1, int blk, int nblk,
-                                      double *__restrict__ part);
-
-// mom != NULL: the blocks from row_blocks on (gridDim.x - row_blocks of them) sum runs of the moment
-// records [m0, m1) (tiles, then the support pass's blocks) into mpart instead (moments_partial_block);
-// blocks [0, row_blocks) reduce the coordinate partials, plus the support pass's per-row term corr
-// (background form) last.
-__global__ __launch_bounds__(1024) void pairdist_reduce_kernel(const float4 *__restrict__ part, int ncol,
-                                                               int N, int nb, int mode, int64_t t0,
-                                                               int64_t t1, float scale,
-                                                               float *__restrict__ dcoords,
-                                                               const double *__restrict__ mom, int64_t m0, int64_t m1,
-                                                               int row_blocks, double *__restrict__ mpart,
-                                                               const float4 *__restrict__ corr, int corr_r0,
-                                                               int corr_r1, double *__restrict__ dc64) {
-  if (mom && (int)blockIdx.x >= row_blocks) {
-    moments_partial_block(mom, m0, m1, (int)blockIdx.x - row_blocks, (int)gridDim.x - row_blocks, mpart);
-    return;
-  }
-  __shared__ float4 red[kRedGroups][64];
-  const int lr64 = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int gi = blockIdx.x * 64 + lr64;
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-  if (gi < N) {
-    const int R = gi / BT, lr = gi % BT;
-#pragma unroll 2
-    for (int J = grp; J < nb; J += kRedGroups) {
-      int64_t trow, tcol;
-      if (mode == MODE_SYM) {
-        trow = J >= R ? tri_start(R, nb) + (J - R) : -1;
-        tcol = J <= R ? tri_start(J, nb) + (R - J) : -1;
-      } else {
-        trow = (int64_t)R * nb + J;
-        tcol = (int64_t)J * nb + R;
-      }
-      // slab of tile t: [row partials | ncol column-partial rows], (1 + ncol) x BT float4
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a;
-      const size_t st = (size_t)(1 + ncol) * BT;
-      if (trow >= t0 && trow < t1) a = part[(size_t)trow * st + lr];
-      if (tcol >= t0 && tcol < t1) {
-        b = part[(size_t)tcol * st + BT + lr];
-        if (ncol == 2) c = part[(size_t)tcol * st + 2 * BT + lr];
-      }
-      sx += a.x; sy += a.y; sz += a.z;
-      sx += b.x; sy += b.y; sz += b.z;
-      sx += c.x; sy += c.y; sz += c.z;
-    }
-  }
-  red[grp][lr64] = make_float4(sx, sy, sz, 0.f);
-  __syncthreads();
-  if (grp == 0 && gi < N) {
-    float4 s0 = red[0][lr64];
-#pragma unroll
-    for (int g = 1; g < kRedGroups; ++g) {
-      const float4 o = red[g][lr64];
-      s0.x += o.x; s0.y += o.y; s0.z += o.z;
-    }
-    if (corr && gi >= corr_r0 && gi < corr_r1) {
-      const float4 o = corr[gi];
-      s0.x += o.x; s0.y += o.y; s0.z += o.z;
-    }
-    const float gx = s0.x * scale, gy = s0.y * scale, gz = s0.z * scale;
-    if (dc64) {   // the fp32 values, widened: straight into a caller's fp64 all-reduce buffer
-      dc64[3 * (size_t)gi] = gx;
-      dc64[3 * (size_t)gi + 1] = gy;
-      dc64[3 * (size_t)gi + 2] = gz;
-    } else {
-      dcoords[3 * (size_t)gi] = gx;
-      dcoords[3 * (size_t)gi + 1] = gy;
-      dcoords[3 * (size_t)gi + 2] = gz;
-    }
-  }
-}
-
-// stats[7..10] and loss from the (all-reduced) moments stats[0..6]: mse, pearson r, alpha, total;
-// contrastive: stats[7] = mean_{i<j} |T - D| (fp64, as the reference's float64 truth makes it),
-// stats[8] = NaN, stats[9] = 0.1, stats[10] = total = 0.1 * stats[7].
-__device__ void finalize_stats(int N, int loss_kind, double *__restrict__ stats, float *__restrict__ loss) {
-  if (loss_kind == KIND_CONTRASTIVE) {
-    const double M = 0.5 * (double)N * (double)(N - 1);
-    const double mae = M > 0.0 ? stats[0] / M : 0.0;
-    const double total = 0.1 * mae;
-    stats[7] = mae;
-    stats[8] = NAN;
-    stats[9] = 0.1;
-    stats[10] = total;
-    stats[11] = 0.0;
-    if (loss) loss[0] = (float)total;
-    return;
-  }
-  const double n2 = (double)N * (double)N;
-  const double mse = (2.0 * stats[0] + stats[6]) / n2;
-  const double M = 0.5 * (double)N * (double)(N - 1);
-  const double sd = stats[1], sdd = stats[2], sdt = stats[3], st = stats[4], stt = stats[5];
-  const double cov = sdt - sd * st / M, vd = sdd - sd * sd / M, vt = stt - st * st / M;
-  const double r = (vd > 0.0 && vt > 0.0) ? cov / sqrt(vd * vt) : NAN;
-  // HiC_GAT_generalize_directly.py:223-225: alpha from mse_loss.item() (the fp32 value), then
-  // total_loss = mse_loss + alpha*(1-r) evaluated as an fp32 tensor + scalar add.
-  const float msef = (float)mse;
-  const double alpha = fmin(1.0, 0.1 + 1.0 / ((double)msef + 1e-6));
-  const float totalf = msef + (float)(alpha * (1.0 - r));
-  stats[7] = mse;
-  stats[8] = r;
-  stats[9] = alpha;
-  stats[10] = (double)totalf;
-  stats[11] = 0.0;
-  if (loss) loss[0] = loss_kind == 1 ? totalf : msef;
-}
-
-__global__ __launch_bounds__(64) void finalize_kernel(int N, int loss_kind, double *__restrict__ stats,
-                                                      float *__restrict__ loss) {
-  if (threadIdx.x == 0) finalize_stats(N, loss_kind, stats, loss);
-}
-
-// Tile moments over [t0,t1) in two fixed-order stages (deterministic): kMomBlocks extra blocks of
-// pairdist_reduce_kernel each sum a contiguous tile run (256 threads, each a strided subset with
-// its loads in flight, then a fixed tree) into part[b][0..6]; moments_finalize_kernel adds the
-// kMomBlocks partials in block order into stats[0..6] and finalizes.  A rank's share whose partial
-// moments are all-reduced before the finalize (the sharded step) with at most kOneBlockMoments
-// records: ONE such block writes stats[0..6] itself (no moments_finalize launch).
-constexpr int kMomBlocks = 64;
-constexpr int64_t kOneBlockMoments = 4096;
-
-__device__ void moments_partial_block(const double *__restrict__ mom, int64_t t0, int64_t t1, int blk, int nblk,
-                                      double *__restrict__ part) {
-  __shared__ double mred[7][256];
-  const int tid = threadIdx.x;
-  const int64_t per = (t1 - t0 + nblk - 1) / nblk;
-  const int64_t b0 = t0 + (int64_t)blk * per, b1 = min(t1, b0 + per);
-  double s[7] = {0, 0, 0, 0, 0, 0, 0};
-  if (tid < 256) {
-    for (int64_t t = b0 + tid; t < b1; t += 256) {
-#pragma unroll
-      for (int c = 0; c < 7; ++c) s[c] += mom[(size_t)t * 8 + c];
-    }
-#pragma unroll
-    for (int c = 0; c < 7; ++c) mred[c][tid] = s[c];
-  }
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-#pragma unroll
-      for (int c = 0; c < 7; ++c) mred[c][tid] += mred[c][tid + o];
-    }
-    __syncthreads();
-  }
-  if (tid < 7) part[blk * 8 + tid] = mred[tid][0];
-}
-
-__global__ __launch_bounds__(64) void moments_finalize_kernel(const double *__restrict__ part, int N, int loss_kind,
-                                                              double *__restrict__ stats, float *__restrict__ loss) {
-  if (threadIdx.x < 7) {
-    double s = 0.0;
-    for (int b = 0; b < kMomBlocks; ++b) s += part[b * 8 + threadIdx.x];
-    stats[threadIdx.x] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) finalize_stats(N, loss_kind, stats, loss);
-}
-
-// Support pass of the background form: T = bg except at the sorted CSR support (symmetric, no
-// diagonal) and the diagonal.  One wave per row i, lanes over its support entries j:
-//   gradient  corr[i] = sum_j ((d - t) - (d - bg)) / d * (c_i - c_j) = sum_j (bg - t) / d * (c_i - c_j)
-//             (every j: the bulk tiles gave row i the bg term of each pair, as row or column partial);
-//   moments   over j > i only (each pair once, in fp64), the support's change of the bulk's terms:
-//             L += (d - t)^2 - (d - bg)^2, sdt += d (t - bg), st += t - bg, stt += t^2 - bg^2; and the
-//             diagonal's (0 - T_ii)^2 into the dg moment.
-// Contrastive (KIND_CONTRASTIVE): corr[i] = sum_j (sgn(d - t) - sgn(d - bg)) / d * (c_i - c_j), and
-// L += |d - t| - |d - bg| over j > i; no diagonal term (the loss is over i < j only).
-// d is formed exactly as in the bulk's interior path.  Per-block moment records (fixed order).
-template <int KIND>
-__device__ void support_block(const float *__restrict__ coords, float bg, int row_begin, int row_end,
-                                              const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                              const float *__restrict__ val, const float *__restrict__ diag,
-                                              float4 *__restrict__ corr, double *__restrict__ mom,
-                                              const int *__restrict__ cmap, int blk, const float4 *__restrict__ cpad) {
-  constexpr bool PEARSON = KIND == KIND_COMBINED, ABSL = KIND == KIND_CONTRASTIVE;
-  __shared__ double mred[4][7];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int i = row_begin + blk * 4 + wv;
-  float gx = 0.f, gy = 0.f, gz = 0.f;
-  double L = 0.0, sdt = 0.0, st = 0.0, stt = 0.0, dg = 0.0;   // the support's moment changes in fp64
-  if (i < row_end) {   // wave-uniform
-    const size_t ic = cmap ? (size_t)cmap[i] : (size_t)i;
-    const float xi = coords[3 * ic], yi = coords[3 * ic + 1], zi = coords[3 * ic + 2];
-    const int e1 = rowptr[i + 1];
-    // four of the lane's entries per round, every index and coordinate load of the round issued before
-    // its arithmetic (one wave per row: the col -> coordinate load chain was the pass's latency)
-    constexpr int SU = 4;
-    for (int e0 = rowptr[i] + lane; e0 < e1; e0 += 64 * SU) {
-      int jj[SU];
-      float tt[SU], cx[SU], cy[SU], cz[SU];
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int e = e0 + 64 * u;
-        jj[u] = e < e1 ? col[e] : i;
-        tt[u] = e < e1 ? val[e] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const size_t jc = cmap ? (size_t)cmap[jj[u]] : (size_t)jj[u];
-        // cpad: the coordinates as float4 rows (one 16-B load per lane instead of three 4-B loads)
-        if (cpad) {
-          const float4 c = cpad[jc];
-          cx[u] = c.x; cy[u] = c.y; cz[u] = c.z;
-        } else {
-          cx[u] = coords[3 * jc]; cy[u] = coords[3 * jc + 1]; cz[u] = coords[3 * jc + 2];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        if (e0 + 64 * u >= e1) break;
-        const int j = jj[u];
-        const float t = tt[u];
-        const float dx = xi - cx[u], dy = yi - cy[u], dz = zi - cz[u];
-        const float d2 = fmaf(dx, dx, fmaf(dy, dy, fmaf(dz, dz, 0x1.0p-100f)));
-        const float inv = __builtin_amdgcn_rsqf(d2);
-        const float d = d2 * inv;
-        const float w = ABSL ? sgn_inv(d - t, inv) - sgn_inv(d - bg, inv) : (bg - t) * inv;
-        gx = fmaf(w, dx, gx);
-        gy = fmaf(w, dy, gy);
-        gz = fmaf(w, dz, gz);
-        if (j > i) {
-          const double dd = d, td = t, bd = bg;
-          const double r = dd - td, rb = dd - bd;
-          L += ABSL ? fabs(r) - fabs(rb) : r * r - rb * rb;
-          if (PEARSON) {
-            sdt += dd * (td - bd);
-            st += td - bd;
-            stt += td * td - bd * bd;
-          }
-        }
-      }
-    }
-    if (lane == 0 && !ABSL) {
-      const float ti = diag[i];
-      dg = (double)ti * (double)ti;
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    gx += __shfl_xor(gx, o);
-    gy += __shfl_xor(gy, o);
-    gz += __shfl_xor(gz, o);
-  }
-  if (i < row_end && lane == 0) corr[i] = make_float4(gx, gy, gz, 0.f);
-  double m[7] = {L, 0.0, 0.0, sdt, st, stt, dg};
-#pragma unroll
-  for (int c = 0; c < 7; ++c) {
-    if (c == 1 || c == 2 || (!PEARSON && c >= 3 && c <= 5)) continue;
-    for (int o = 32; o > 0; o >>= 1) m[c] += shfl_xor_d(m[c], o);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int c = 0; c < 7; ++c) mred[wv][c] = m[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < 7)
-    mom[(size_t)blk * 8 + threadIdx.x] =
-        ((mred[0][threadIdx.x] + mred[1][threadIdx.x]) + mred[2][threadIdx.x]) + mred[3][threadIdx.x];
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void pairdist_support_kernel(const float *__restrict__ coords, int N, float bg,
-                                                               int row_begin, int row_end,
-                                                               const int32_t *__restrict__ rowptr,
-                                                               const int32_t *__restrict__ col,
-                                                               const float *__restrict__ val,
-                                                               const float *__restrict__ diag,
-                                                               float4 *__restrict__ corr, double *__restrict__ mom,
-                                                               const int *__restrict__ cmap,
-                                                               const float4 *__restrict__ cpad = nullptr) {
-  support_block<KIND>(coords, bg, row_begin, row_end, rowptr, col, val, diag, corr, mom, cmap, blockIdx.x, cpad);
-}
-
-// D[i, j] = ||c_i - c_j||: one thread per element.
-__global__ __launch_bounds__(256) void pairdist_fwd_kernel(const float *__restrict__ coords, int N,
-                                                           float *__restrict__ D, int64_t ldd) {
-  __shared__ float ci[3];
-  const int i = blockIdx.y;
-  if (threadIdx.x < 3) ci[threadIdx.x] = coords[3 * (size_t)i + threadIdx.x];
-  __syncthreads();
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= N) return;
-  const float dx = ci[0] - coords[3 * (size_t)j], dy = ci[1] - coords[3 * (size_t)j + 1],
-              dz = ci[2] - coords[3 * (size_t)j + 2];
-  D[(size_t)i * ldd + j] = i == j ? 0.f : sqrtf(fmaf(dx, dx, fmaf(dy, dy, dz * dz)));
-}
-
 // ---- moment-dependent losses (mse + alpha (1 - r), rmse, scale-invariant mse) ---------------------
 // Their derivative per pair is g_ij = A d_ij + B t_ij + C with A, B, C functions of the global
 // moments, which are only known after the pass.  With u_ij = (c_i - c_j) / d_ij (0 where d_ij = 0):
@@ -806,7 +343,6 @@ __global__ __launch_bounds__(256) void pairdist_fwd_kernel(const float *__restri
 enum { MLOSS_PEARSON = HICGAT_MLOSS_PEARSON, MLOSS_RMSE = HICGAT_MLOSS_RMSE, MLOSS_SI_MSE = HICGAT_MLOSS_SI_MSE };
 
 constexpr int kMPlanes = 6;   // row partial planes in LDS: R x/y/z, W x/y/z
-constexpr int kMSlabs = 4;    // float4 slabs per tile: R rows, R columns, W rows, W columns
 constexpr double kVarFloor = 0x1.0p-20;   // see mloss_finalize_kernel
 
 // Per-thread accumulators of one tile, packed: the column partials of R and W for the thread's 8
@@ -909,6 +445,334 @@ __device__ __forceinline__ void mloss_rows(const float *__restrict__ T, int64_t 
   }
 }
 
+// Support pass of the background form: T = bg except at the sorted CSR support (symmetric, no
+// diagonal) and the diagonal.  One wave per row i, lanes over its support entries j:
+//   gradient  corr[i] = sum_j ((d - t) - (d - bg)) / d * (c_i - c_j) = sum_j (bg - t) / d * (c_i - c_j)
+//             (every j: the bulk tiles gave row i the bg term of each pair, as row or column partial);
+//   moments   over j > i only (each pair once, in fp64), the support's change of the bulk's terms:
+//             L += (d - t)^2 - (d - bg)^2, sdt += d (t - bg), st += t - bg, stt += t^2 - bg^2; and the
+//             diagonal's (0 - T_ii)^2 into the dg moment.
+// Contrastive (KIND_CONTRASTIVE): corr[i] = sum_j (sgn(d - t) - sgn(d - bg)) / d * (c_i - c_j), and
+// L += |d - t| - |d - bg| over j > i; no diagonal term (the loss is over i < j only).
+// d is formed exactly as in the bulk's interior path.  Per-block moment records (fixed order).
+template <int KIND>
+__device__ void support_block(const float *__restrict__ coords, float bg, int row_begin, int row_end,
+                              const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                              const float *__restrict__ val, const float *__restrict__ diag, float4 *__restrict__ corr,
+                              double *__restrict__ mom, const int *__restrict__ cmap, int blk,
+                              const float4 *__restrict__ cpad = nullptr) {
+  constexpr bool PEARSON = KIND == KIND_COMBINED, ABSL = KIND == KIND_CONTRASTIVE;
+  __shared__ double mred[4][7];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int i = row_begin + blk * 4 + wv;
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  double L = 0.0, sdt = 0.0, st = 0.0, stt = 0.0, dg = 0.0;   // the support's moment changes in fp64
+  if (i < row_end) {   // wave-uniform
+    const size_t ic = cmap ? (size_t)cmap[i] : (size_t)i;
+    const float xi = coords[3 * ic], yi = coords[3 * ic + 1], zi = coords[3 * ic + 2];
+    const int e1 = rowptr[i + 1];
+    // four of the lane's entries per round, every index and coordinate load of the round issued before
+    // its arithmetic (one wave per row: the col -> coordinate load chain was the pass's latency)
+    constexpr int SU = 4;
+    for (int e0 = rowptr[i] + lane; e0 < e1; e0 += 64 * SU) {
+      int jj[SU];
+      float tt[SU], cx[SU], cy[SU], cz[SU];
+#pragma unroll
+      for (int u = 0; u < SU; ++u) {
+        const int e = e0 + 64 * u;
+        jj[u] = e < e1 ? col[e] : i;
+        tt[u] = e < e1 ? val[e] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < SU; ++u) {
+        const size_t jc = cmap ? (size_t)cmap[jj[u]] : (size_t)jj[u];
+        // cpad: the coordinates as float4 rows (one 16-B load per lane instead of three 4-B loads)
+        if (cpad) {
+          const float4 c = cpad[jc];
+          cx[u] = c.x; cy[u] = c.y; cz[u] = c.z;
+        } else {
+          cx[u] = coords[3 * jc]; cy[u] = coords[3 * jc + 1]; cz[u] = coords[3 * jc + 2];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < SU; ++u) {
+        if (e0 + 64 * u >= e1) break;
+        const int j = jj[u];
+        const float t = tt[u];
+        const float dx = xi - cx[u], dy = yi - cy[u], dz = zi - cz[u];
+        const float d2 = fmaf(dx, dx, fmaf(dy, dy, fmaf(dz, dz, 0x1.0p-100f)));
+        const float inv = __builtin_amdgcn_rsqf(d2);
+        const float d = d2 * inv;
+        const float w = ABSL ? sgn_inv(d - t, inv) - sgn_inv(d - bg, inv) : (bg - t) * inv;
+        gx = fmaf(w, dx, gx);
+        gy = fmaf(w, dy, gy);
+        gz = fmaf(w, dz, gz);
+        if (j > i) {
+          const double dd = d, td = t, bd = bg;
+          const double r = dd - td, rb = dd - bd;
+          L += ABSL ? fabs(r) - fabs(rb) : r * r - rb * rb;
+          if (PEARSON) {
+            sdt += dd * (td - bd);
+            st += td - bd;
+            stt += td * td - bd * bd;
+          }
+        }
+      }
+    }
+    if (lane == 0 && !ABSL) {
+      const float ti = diag[i];
+      dg = (double)ti * (double)ti;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    gx += __shfl_xor(gx, o);
+    gy += __shfl_xor(gy, o);
+    gz += __shfl_xor(gz, o);
+  }
+  if (i < row_end && lane == 0) corr[i] = make_float4(gx, gy, gz, 0.f);
+  // sum d and sum d^2 (1, 2) do not change; sdt, st, stt (3..5) only for the Pearson term
+  double m[7] = {L, 0.0, 0.0, sdt, st, stt, dg};
+  moment_wave_sums<7, PEARSON ? 0x79u : 0x41u>(m, mred, lane, wv);
+  __syncthreads();
+  moment_record<7>(mred, mom + (size_t)blk * 8);
+}
+
+// ---- tile prologue and epilogue, both chains ------------------------------------------------------
+
+// The coordinate rows of row block I into sc[0] and of column block J into sc[1] (0 past N).  cmap:
+// global row -> coords row (sharded step).  cpad: the diagonal tile of row block I writes its rows'
+// float4 copy for the support pass that follows.
+__device__ __forceinline__ void stage_coords(const float *__restrict__ coords, const int *__restrict__ cmap,
+                                             float4 *__restrict__ cpad, int N, int I, int J, float (*sc)[BT][3]) {
+  for (int k = threadIdx.x; k < 2 * BT; k += 256) {
+    const int which = k / BT, li = k % BT;
+    const int g = (which ? J : I) * BT + li;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (g < N) {
+      const size_t gc = cmap ? (size_t)cmap[g] : (size_t)g;
+      x = coords[3 * gc];
+      y = coords[3 * gc + 1];
+      z = coords[3 * gc + 2];
+    }
+    sc[which][li][0] = x;
+    sc[which][li][1] = y;
+    sc[which][li][2] = z;
+    if (cpad && I == J && which == 0 && g < N) cpad[g] = make_float4(x, y, z, 0.f);
+  }
+}
+
+// Column partials of P planes (a[plane]: the thread's 8 columns, summed in place): each value over the
+// 4 ty of its wave (lanes l, l^16, l^32, l^48), then lanes < 16 write colred[plane][wave][column]; after
+// a barrier col_sums adds the 4 waves in order.
+template <int P>
+__device__ __forceinline__ void col_partials(float *const (&a)[P], float (*colred)[4][BT], int tx, int lane, int wv) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+#pragma unroll
+    for (int c = 0; c < P; ++c) a[c][q] = sum_rows4(a[c][q]);
+  }
+  if (lane < 16) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int lc = tx * 4 + (q & 3) + (q >> 2) * 64;
+#pragma unroll
+      for (int c = 0; c < P; ++c) colred[c][wv][lc] = a[c][q];
+    }
+  }
+}
+
+template <int P>
+__device__ __forceinline__ void col_sums(const float (*colred)[4][BT], int lc, float (&s)[P]) {
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+    s[c] = colred[c][0][lc];
+#pragma unroll
+    for (int w2 = 1; w2 < 4; ++w2) s[c] += colred[c][w2][lc];
+  }
+}
+
+// Row lr of P rowpart planes: its 16 per-thread partials (four 16-B loads) added in tx order.
+template <int P>
+__device__ __forceinline__ void row_sums(const float *rowpart, int lr, float (&s)[P]) {
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+    float v[16];
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const float4 o = *reinterpret_cast<const float4 *>(&rowpart[c * kRowPlane + lr * kRowPad + 4 * q4]);
+      v[4 * q4] = o.x; v[4 * q4 + 1] = o.y; v[4 * q4 + 2] = o.z; v[4 * q4 + 3] = o.w;
+    }
+    s[c] = v[0];
+#pragma unroll
+    for (int q = 1; q < 16; ++q) s[c] += v[q];   // tx order, as the 16 entries were always added
+  }
+}
+
+// ---- the tile kernels -----------------------------------------------------------------------------
+
+// The support pass riding in the background-form tile launch (SUP): blocks [ntiles, ntiles +
+// blocks) of the grid run pairdist_support_kernel's work for support block (blockIdx.x - ntiles).
+struct SupportArgs {
+  const int32_t *rowptr = nullptr, *col = nullptr;
+  const float *val = nullptr, *diag = nullptr;
+  float4 *corr = nullptr;
+  double *mom = nullptr;
+  int row_begin = 0, row_end = 0;
+  int64_t ntiles = 0;
+};
+
+// MODE_SYM: T = symmetric truth, tiles I <= J, pairs i < j, w = (d - t)/d (scale 4/N^2 later).
+// MODE_FULL: T = upstream grad G of D, all tiles, pairs i != j, w = g/d.
+// KIND: KIND_MSE: sum (d - t)^2; KIND_COMBINED: also the d / t moments of the Pearson term;
+// KIND_CONTRASTIVE: sum |d - t| and w = sgn(d - t) / d.
+// BG: the background form (T = bg at every pair; no T read, no diagonal term -- the support pass,
+// pairdist_support_kernel, adds the entries that differ and the diagonal).
+// The background form is latency-bound and is built for four workgroups per CU: <= 128 VGPRs (the
+// launch bound makes the compiler hold to them) and <= 40 KB of LDS; tests/test_pairdist_resources_host.py
+// checks both from the kernel metadata.
+template <int MODE, bool VEC, int KIND, bool BG = false, bool SUP = false>
+__global__ __launch_bounds__(256, BG ? 4 : 1) void pairdist_tile_kernel(const float *__restrict__ coords,
+                                                            const float *__restrict__ T, int N,
+                                                            int64_t ldt, int64_t row0, int64_t col0,
+                                                            int nb, int64_t t0,
+                                                            float4 *__restrict__ part,
+                                                            double *__restrict__ mom, float bg,
+                                                            const int *__restrict__ cmap = nullptr,
+                                                            const SupportArgs sup = SupportArgs{},
+                                                            float4 *__restrict__ cpad = nullptr) {
+  static_assert(!BG || (MODE == MODE_SYM && !VEC), "the background form is the training loss without a T image");
+  static_assert(!SUP || BG, "the support pass rides only in the background form's launch");
+  if (SUP && (int64_t)blockIdx.x >= sup.ntiles) {   // block-uniform
+    support_block<KIND>(coords, bg, sup.row_begin, sup.row_end, sup.rowptr, sup.col, sup.val, sup.diag, sup.corr,
+                           sup.mom, cmap, (int)(blockIdx.x - sup.ntiles));
+    return;
+  }
+  // one dynamic LDS array: [T tile 128x128 fp32 (VEC only)] -- 64 KiB, 16-B aligned
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  __shared__ float sc[2][BT][3];
+  __shared__ float colred[3][4][BT];   // planar x / y / z: [wave][column]
+  __shared__ double mred[4][7];
+  constexpr bool RL = BG;
+  __shared__ __attribute__((aligned(16))) float rowpart_s[RL ? 3 * kRowPlane : 1];
+  float *rowpart = RL ? rowpart_s : nullptr;
+  const int64_t t = t0 + blockIdx.x;
+  int I, J;
+  if (MODE == MODE_SYM) {
+    tri_decode(t, nb, I, J);
+  } else {
+    I = (int)(t / nb);
+    J = (int)(t % nb);
+  }
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lane = tid & 63, wv = tid >> 6;
+  stage_coords(coords, cmap, cpad, N, I, J, sc);
+  if (VEC) {
+    // LDS-DMA of the T tile (global_load_lds_dwordx4: each wave instruction moves 1 KiB = two 512-B
+    // tile rows, wave-uniform LDS base + lane*16), each wave only the 32 rows its threads read:
+    // rows 16w .. 16w+15 (k = 0..3 of tile_rows) first, then 64+16w .. 64+16w+15 (k = 4..7), so the
+    // first half is computed while the second is in flight.  Rows past N are clamped to a valid row
+    // (their values are masked); columns past N lie inside the padded leading dimension.  T may be
+    // a band of the truth (rows from row0, columns from col0: a rank's share, hicgat.dist).
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int r0 = (q < 8 ? 0 : 64) + wv * 16 + (q & 7) * 2;
+      const int gi = min(I * BT + r0 + (lane >> 5), N - 1);
+      const float *src = T + (size_t)(gi - row0) * ldt + (size_t)((int64_t)J * BT - col0) + (lane & 31) * 4;
+      __builtin_amdgcn_global_load_lds(src, &tile[r0 * BT], 16, 0, 0);
+    }
+  }
+  // sc[] (written above with ds_write) to all waves: LDS drain + raw barrier -- __syncthreads()
+  // would also drain vmcnt and so wait for the whole tile
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+
+  float cx[8], cy[8], cz[8];
+  const int gj0 = J * BT + tx * 4;
+  TileAcc A;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int lc = tx * 4 + (q & 3) + (q >> 2) * 64;
+    cx[q] = sc[1][lc][0];
+    cy[q] = sc[1][lc][1];
+    cz[q] = sc[1][lc][2];
+    A.ax[q] = A.ay[q] = A.az[q] = 0.f;
+  }
+  float4 *prow = part + (size_t)t * 2 * BT;
+  const bool interior = I != J && (I + 1) * BT <= N && (J + 1) * BT <= N;   // block-uniform
+  if (VEC) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // this wave's first 16 rows landed
+  constexpr bool PK = (VEC || BG) && MODE == MODE_SYM;   // packed interior path (tile_rows_pk)
+  if constexpr (BG) {
+    // no T image to wait for between the halves: one branch around both, so the interior and the
+    // masked form never share a live range (the two half-calls stay: each half's moments are
+    // summed on their own and then added, the order the records have always had)
+    if (interior) {
+      tile_rows_pk<KIND, 0, 4, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
+      tile_rows_pk<KIND, 4, 8, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
+    } else {
+      tile_rows<MODE, VEC, KIND, true, 0, 4, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+      tile_rows<MODE, VEC, KIND, true, 4, 8, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    }
+  } else {
+    if (interior) {
+      if constexpr (PK) tile_rows_pk<KIND, 0, 4, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
+      else tile_rows<MODE, VEC, KIND, false, 0, 4>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    } else {
+      tile_rows<MODE, VEC, KIND, true, 0, 4, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    }
+    if (VEC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // and the second 16
+    if (interior) {
+      if constexpr (PK) tile_rows_pk<KIND, 4, 8, BG, RL>(tile, bg, sc, tx, ty, cx, cy, cz, prow, A, rowpart);
+      else tile_rows<MODE, VEC, KIND, false, 4, 8>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    } else {
+      tile_rows<MODE, VEC, KIND, true, 4, 8, BG, RL>(T, ldt, row0, col0, N, I, J, bg, tile, sc, tx, ty, cx, cy, cz, gj0, prow, A, rowpart);
+    }
+  }
+
+  float *const planes[3] = {A.ax, A.ay, A.az};
+  col_partials<3>(planes, colred, tx, lane, wv);
+  if (MODE == MODE_SYM) {
+    // the Pearson moments (1..5) only for the combined loss; the others stay 0 in every lane
+    double m[7] = {A.L, A.sd, A.sdd, A.sdt, A.st, A.stt, A.dg};
+    moment_wave_sums<7, KIND == KIND_COMBINED ? 0x7Fu : 0x41u>(m, mred, lane, wv);
+  }
+  __syncthreads();
+  float s[3];
+  if (tid < BT) {
+    col_sums<3>(colred, tid, s);
+    prow[BT + tid] = make_float4(s[0], s[1], s[2], 0.f);
+  } else if (RL) {   // the other forms took their row partials from sum16 inside the pair loop
+    row_sums<3>(rowpart, tid - BT, s);
+    prow[tid - BT] = make_float4(s[0], s[1], s[2], 0.f);
+  }
+  if (MODE == MODE_SYM) moment_record<7>(mred, mom + (size_t)t * 8);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void pairdist_support_kernel(const float *__restrict__ coords, int N, float bg,
+                                                               int row_begin, int row_end,
+                                                               const int32_t *__restrict__ rowptr,
+                                                               const int32_t *__restrict__ col,
+                                                               const float *__restrict__ val,
+                                                               const float *__restrict__ diag,
+                                                               float4 *__restrict__ corr, double *__restrict__ mom,
+                                                               const int *__restrict__ cmap,
+                                                               const float4 *__restrict__ cpad = nullptr) {
+  support_block<KIND>(coords, bg, row_begin, row_end, rowptr, col, val, diag, corr, mom, cmap, blockIdx.x, cpad);
+}
+
+// D[i, j] = ||c_i - c_j||: one thread per element.
+__global__ __launch_bounds__(256) void pairdist_fwd_kernel(const float *__restrict__ coords, int N,
+                                                           float *__restrict__ D, int64_t ldd) {
+  __shared__ float ci[3];
+  const int i = blockIdx.y;
+  if (threadIdx.x < 3) ci[threadIdx.x] = coords[3 * (size_t)i + threadIdx.x];
+  __syncthreads();
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= N) return;
+  const float dx = ci[0] - coords[3 * (size_t)j], dy = ci[1] - coords[3 * (size_t)j + 1],
+              dz = ci[2] - coords[3 * (size_t)j + 2];
+  D[(size_t)i * ldd + j] = i == j ? 0.f : sqrtf(fmaf(dx, dx, fmaf(dy, dy, dz * dz)));
+}
+
 // One 256-thread block per upper-triangle 128x128 tile, whole matrix only.  Writes, per tile, four
 // [128] float4 slabs (R row partials, R column partials, W row partials, W column partials) and one
 // moment record of 8 doubles: sum (d-t)^2, sum d, sum d^2, sum dt, sum t, sum t^2, sum T_ii^2,
@@ -927,21 +791,7 @@ __global__ __launch_bounds__(256, 2) void pairdist_mloss_tile_kernel(const float
   int I, J;
   tri_decode(t, nb, I, J);
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lane = tid & 63, wv = tid >> 6;
-  for (int k = tid; k < 2 * BT; k += 256) {
-    const int which = k / BT, li = k % BT;
-    const int g = (which ? J : I) * BT + li;
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (g < N) {
-      x = coords[3 * (size_t)g];
-      y = coords[3 * (size_t)g + 1];
-      z = coords[3 * (size_t)g + 2];
-    }
-    sc[which][li][0] = x;
-    sc[which][li][1] = y;
-    sc[which][li][2] = z;
-    // the diagonal tile of row block I writes its rows' float4 copy for the support pass that follows
-    if (cpad && I == J && which == 0 && g < N) cpad[g] = make_float4(x, y, z, 0.f);
-  }
+  stage_coords(coords, nullptr, cpad, N, I, J, sc);
   __syncthreads();
 
   f2 cx2[4], cy2[4], cz2[4];
@@ -970,75 +820,165 @@ __global__ __launch_bounds__(256, 2) void pairdist_mloss_tile_kernel(const float
     mloss_rows<true, BG>(T, ldt, vec != 0, N, I, J, bg, sc, tx, ty, cx2, cy2, cz2, gj0, A, rowpart);
   }
 
-  // column partials: reduce over the 4 ty of this wave (lanes l, l^16, l^32, l^48), then waves
-  const auto col_plane = [&](const f2 (&p)[4], int c) {
+  float a[kMPlanes][8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float v = sum_rows4((q & 1) ? p[q >> 1].y : p[q >> 1].x);
-      const int lc = tx * 4 + (q & 3) + (q >> 2) * 64;
-      if (lane < 16) colred[c][wv][lc] = v;
-    }
-  };
-  col_plane(A.ax, 0);
-  col_plane(A.ay, 1);
-  col_plane(A.az, 2);
-  col_plane(A.bx, 3);
-  col_plane(A.by, 4);
-  col_plane(A.bz, 5);
-  {
-    double m[8] = {(double)A.L.x + (double)A.L.y,     (double)A.sd.x + (double)A.sd.y,
-                   (double)A.sdd.x + (double)A.sdd.y, (double)A.sdt.x + (double)A.sdt.y,
-                   (double)A.st.x + (double)A.st.y,   (double)A.stt.x + (double)A.stt.y,
-                   A.dg,                              A.sg};
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      for (int o = 32; o > 0; o >>= 1) m[c] += shfl_xor_d(m[c], o);
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c) mred[wv][c] = m[c];
-    }
+  for (int h = 0; h < 4; ++h) {
+    a[0][2 * h] = A.ax[h].x; a[0][2 * h + 1] = A.ax[h].y;
+    a[1][2 * h] = A.ay[h].x; a[1][2 * h + 1] = A.ay[h].y;
+    a[2][2 * h] = A.az[h].x; a[2][2 * h + 1] = A.az[h].y;
+    a[3][2 * h] = A.bx[h].x; a[3][2 * h + 1] = A.bx[h].y;
+    a[4][2 * h] = A.by[h].x; a[4][2 * h + 1] = A.by[h].y;
+    a[5][2 * h] = A.bz[h].x; a[5][2 * h + 1] = A.bz[h].y;
   }
+  float *const planes[kMPlanes] = {a[0], a[1], a[2], a[3], a[4], a[5]};
+  col_partials<kMPlanes>(planes, colred, tx, lane, wv);
+  double m[8] = {(double)A.L.x + (double)A.L.y,     (double)A.sd.x + (double)A.sd.y,
+                 (double)A.sdd.x + (double)A.sdd.y, (double)A.sdt.x + (double)A.sdt.y,
+                 (double)A.st.x + (double)A.st.y,   (double)A.stt.x + (double)A.stt.y,
+                 A.dg,                              A.sg};
+  moment_wave_sums<8>(m, mred, lane, wv);
   __syncthreads();
-  float4 *prow = part + (size_t)t * kMSlabs * BT;
+  float4 *prow = part + (size_t)t * 4 * BT;   // slabs: R rows, R columns, W rows, W columns
+  float s[kMPlanes];
   if (tid < BT) {
-    float s[kMPlanes];
-#pragma unroll
-    for (int c = 0; c < kMPlanes; ++c) {
-      s[c] = colred[c][0][tid];
-#pragma unroll
-      for (int w2 = 1; w2 < 4; ++w2) s[c] += colred[c][w2][tid];
-    }
+    col_sums<kMPlanes>(colred, tid, s);
     prow[BT + tid] = make_float4(s[0], s[1], s[2], 0.f);
     prow[3 * BT + tid] = make_float4(s[3], s[4], s[5], 0.f);
   } else {
-    const int lr = tid - BT;
-    float s[kMPlanes];
-#pragma unroll
-    for (int c = 0; c < kMPlanes; ++c) {
-      float v[16];
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 o = *reinterpret_cast<const float4 *>(&rowpart[c * kRowPlane + lr * kRowPad + 4 * q4]);
-        v[4 * q4] = o.x; v[4 * q4 + 1] = o.y; v[4 * q4 + 2] = o.z; v[4 * q4 + 3] = o.w;
-      }
-      s[c] = v[0];
-#pragma unroll
-      for (int q = 1; q < 16; ++q) s[c] += v[q];   // tx order
-    }
-    prow[lr] = make_float4(s[0], s[1], s[2], 0.f);
-    prow[2 * BT + lr] = make_float4(s[3], s[4], s[5], 0.f);
+    row_sums<kMPlanes>(rowpart, tid - BT, s);
+    prow[tid - BT] = make_float4(s[0], s[1], s[2], 0.f);
+    prow[2 * BT + tid - BT] = make_float4(s[3], s[4], s[5], 0.f);
   }
-  if (tid < 8) mom[(size_t)t * 8 + tid] = ((mred[0][tid] + mred[1][tid]) + mred[2][tid]) + mred[3][tid];
+  moment_record<8>(mred, mom + (size_t)t * 8);
 }
 
-// Second stage, one launch of 1024-thread blocks:
-//   blocks [0, row_blocks): R_i and W_i of 64 rows each -- the row slabs of tiles (R, J >= R) and the
-//     column slabs of tiles (J <= R, R), 16 J-groups added in group order, then corr[i] (the support
-//     pass's change of R_i, background form) -- into rw[i] (R) and rw[N + i] (W);
-//   blocks [row_blocks, row_blocks + kMomBlocks): runs of the moment records: components 0..6 over
-//     [0, m_all) (tiles, then the support pass's blocks), component 7 over the tiles only (the support
-//     pass's records have no such entry);
+// ---- second stage: per-row slab sums and moment partials ------------------------------------------
+
+constexpr int kRedGroups = 16;   // J-groups per row in the reduce kernels (1024-thread blocks)
+
+// Tile moments in two fixed-order stages (deterministic): kMomBlocks extra blocks of the reduce kernel
+// each sum a contiguous run of records (moments_partial_block) into mpart[b][0..M); the finalize adds
+// the kMomBlocks partials in block order.  A rank's share whose partial moments are all-reduced before
+// the finalize (the sharded step) with at most kOneBlockMoments records: ONE such block writes
+// stats[0..6] itself (no moments_finalize launch).
+constexpr int kMomBlocks = 64;
+constexpr int64_t kOneBlockMoments = 4096;
+
+// Row lr of row block R: group grp's share (J = grp, grp + kRedGroups, ...) of the S sums over the
+// tiles touching the row -- sum s adds slab 2s (row partials) of tile (R, J) and slab 2s + 1 (column
+// partials) of tile (J, R), of 2S [128] float4 slabs per tile; only tiles in [t0, t1).  MODE_SYM:
+// upper-triangle tiles, so the row slab for J >= R and the column slab for J <= R.
+template <int S>
+__device__ __forceinline__ void gather_row(const float4 *__restrict__ part, int nb, int mode, int64_t t0, int64_t t1,
+                                           int R, int lr, int grp, float4 (&sum)[S]) {
+  const size_t st = (size_t)(2 * S) * BT;
+#pragma unroll 2
+  for (int J = grp; J < nb; J += kRedGroups) {
+    int64_t trow, tcol;
+    if (mode == MODE_SYM) {
+      trow = J >= R ? tri_start(R, nb) + (J - R) : -1;
+      tcol = J <= R ? tri_start(J, nb) + (R - J) : -1;
+    } else {
+      trow = (int64_t)R * nb + J;
+      tcol = (int64_t)J * nb + R;
+    }
+    const bool has_row = trow >= t0 && trow < t1, has_col = tcol >= t0 && tcol < t1;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+      if (has_row) a = part[(size_t)trow * st + (2 * s) * BT + lr];
+      if (has_col) b = part[(size_t)tcol * st + (2 * s + 1) * BT + lr];
+      add3(sum[s], a);
+      add3(sum[s], b);
+    }
+  }
+}
+
+// the kRedGroups group sums red[group][64] of one row, added in group order
+__device__ __forceinline__ float4 group_sum(const float4 *red, int lr64) {
+  float4 s = red[lr64];
+#pragma unroll
+  for (int g = 1; g < kRedGroups; ++g) add3(s, red[g * 64 + lr64]);
+  return s;
+}
+
+// Block blk of nblk sums its run of the moment records [t0, t1) into part[blk][0..M): 256 threads, each
+// a strided subset with its loads in flight, then a fixed tree over buf [M][256].  M = 8: component 7
+// only over the records below t7 (the tiles: the support pass's records have no such entry).
+template <int M>
+__device__ __forceinline__ void moments_partial_block(const double *__restrict__ mom, int64_t t0, int64_t t1,
+                                                      int64_t t7, int blk, int nblk, double *__restrict__ part,
+                                                      double *buf) {
+  const int tid = threadIdx.x;
+  const int64_t per = (t1 - t0 + nblk - 1) / nblk;
+  const int64_t b0 = t0 + (int64_t)blk * per, b1 = min(t1, b0 + per);
+  if (tid < 256) {
+    double s[M] = {};
+    for (int64_t t = b0 + tid; t < b1; t += 256) {
+#pragma unroll
+      for (int c = 0; c < 7; ++c) s[c] += mom[(size_t)t * 8 + c];
+      if (M == 8 && t < t7) s[M - 1] += mom[(size_t)t * 8 + 7];
+    }
+#pragma unroll
+    for (int c = 0; c < M; ++c) buf[c * 256 + tid] = s[c];
+  }
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+#pragma unroll
+      for (int c = 0; c < M; ++c) buf[c * 256 + tid] += buf[c * 256 + tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid < M) part[blk * 8 + tid] = buf[tid * 256];
+}
+
+// dcoords[i] = scale * (sum of the row partials of tiles (R, *) + column partials of (*, R)), the slab
+// of a tile being [row partials | column partials].  Block = 64 rows x kRedGroups groups; the group
+// sums are combined in group order (fixed order: bitwise reproducible), then the support pass's
+// per-row term corr (background form).
+// mom != NULL: the blocks from row_blocks on (gridDim.x - row_blocks of them) sum runs of the moment
+// records [m0, m1) (tiles, then the support pass's blocks) into mpart instead (moments_partial_block).
+__global__ __launch_bounds__(1024) void pairdist_reduce_kernel(const float4 *__restrict__ part, int N, int nb,
+                                                               int mode, int64_t t0, int64_t t1, float scale,
+                                                               float *__restrict__ dcoords,
+                                                               const double *__restrict__ mom, int64_t m0, int64_t m1,
+                                                               int row_blocks, double *__restrict__ mpart,
+                                                               const float4 *__restrict__ corr, int corr_r0,
+                                                               int corr_r1, double *__restrict__ dc64) {
+  if (mom && (int)blockIdx.x >= row_blocks) {
+    __shared__ double mbuf[7 * 256];
+    moments_partial_block<7>(mom, m0, m1, 0, (int)blockIdx.x - row_blocks, (int)gridDim.x - row_blocks, mpart, mbuf);
+    return;
+  }
+  __shared__ float4 red[kRedGroups * 64];
+  const int lr64 = threadIdx.x & 63, grp = threadIdx.x >> 6;
+  const int gi = blockIdx.x * 64 + lr64;
+  float4 sum[1] = {make_float4(0.f, 0.f, 0.f, 0.f)};
+  if (gi < N) gather_row<1>(part, nb, mode, t0, t1, gi / BT, gi % BT, grp, sum);
+  red[grp * 64 + lr64] = sum[0];
+  __syncthreads();
+  if (grp == 0 && gi < N) {
+    float4 s0 = group_sum(red, lr64);
+    if (corr && gi >= corr_r0 && gi < corr_r1) add3(s0, corr[gi]);
+    const float gx = s0.x * scale, gy = s0.y * scale, gz = s0.z * scale;
+    if (dc64) {   // the fp32 values, widened: straight into a caller's fp64 all-reduce buffer
+      dc64[3 * (size_t)gi] = gx;
+      dc64[3 * (size_t)gi + 1] = gy;
+      dc64[3 * (size_t)gi + 2] = gz;
+    } else {
+      dcoords[3 * (size_t)gi] = gx;
+      dcoords[3 * (size_t)gi + 1] = gy;
+      dcoords[3 * (size_t)gi + 2] = gz;
+    }
+  }
+}
+
+// The moment-dependent chain's second stage, one launch of 1024-thread blocks over the whole range:
+//   blocks [0, row_blocks): R_i and W_i of 64 rows each (gather_row, the group sums in group order,
+//     then corr[i], the support pass's change of R_i, background form) into rw[i] (R) and rw[N + i] (W);
+//   blocks [row_blocks, row_blocks + kMomBlocks): runs of the moment records [0, m_all), component 7
+//     over the m_tiles tile records only;
 //   the last block: sum_j c_j (x, y, z) and sum_i diag[i] (background form; else 0) in fp64 -> csum[4].
 // Every sum has a fixed order.
 __global__ __launch_bounds__(1024) void pairdist_mloss_reduce_kernel(const float4 *__restrict__ part, int N, int nb,
@@ -1074,80 +1014,125 @@ __global__ __launch_bounds__(1024) void pairdist_mloss_reduce_kernel(const float
     if (tid < 4) csum[tid] = shbuf[tid * 1024];
     return;
   }
-  if (blk >= row_blocks) {   // moment partials
-    const int b = blk - row_blocks;
-    const int64_t per = (m_all + kMomBlocks - 1) / kMomBlocks;
-    const int64_t b0 = (int64_t)b * per, b1 = min(m_all, b0 + per);
-    if (tid < 256) {
-      double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int64_t t = b0 + tid; t < b1; t += 256) {
-#pragma unroll
-        for (int c = 0; c < 7; ++c) s[c] += mom[(size_t)t * 8 + c];
-        if (t < m_tiles) s[7] += mom[(size_t)t * 8 + 7];
-      }
-#pragma unroll
-      for (int c = 0; c < 8; ++c) shbuf[c * 256 + tid] = s[c];
-    }
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (tid < o) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) shbuf[c * 256 + tid] += shbuf[c * 256 + tid + o];
-      }
-      __syncthreads();
-    }
-    if (tid < 8) mpart[b * 8 + tid] = shbuf[tid * 256];
+  if (blk >= row_blocks) {
+    moments_partial_block<8>(mom, 0, m_all, m_tiles, blk - row_blocks, kMomBlocks, mpart, shbuf);
     return;
   }
   float4 *red = reinterpret_cast<float4 *>(shbuf);   // [2][kRedGroups][64]
   const int lr64 = tid & 63, grp = tid >> 6;
   const int gi = blk * 64 + lr64;
-  float4 sr = make_float4(0.f, 0.f, 0.f, 0.f), sw = sr;
-  if (gi < N) {
-    const int R = gi / BT, lr = gi % BT;
-    const size_t st = (size_t)kMSlabs * BT;
-#pragma unroll 2
-    for (int J = grp; J < nb; J += kRedGroups) {
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a, d = a;
-      if (J >= R) {
-        const size_t trow = (size_t)(tri_start(R, nb) + (J - R));
-        a = part[trow * st + lr];
-        c = part[trow * st + 2 * BT + lr];
-      }
-      if (J <= R) {
-        const size_t tcol = (size_t)(tri_start(J, nb) + (R - J));
-        b = part[tcol * st + BT + lr];
-        d = part[tcol * st + 3 * BT + lr];
-      }
-      sr.x += a.x; sr.y += a.y; sr.z += a.z;
-      sr.x += b.x; sr.y += b.y; sr.z += b.z;
-      sw.x += c.x; sw.y += c.y; sw.z += c.z;
-      sw.x += d.x; sw.y += d.y; sw.z += d.z;
-    }
-  }
-  red[grp * 64 + lr64] = sr;
-  red[(kRedGroups + grp) * 64 + lr64] = sw;
+  float4 sum[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};   // R, W
+  if (gi < N) gather_row<2>(part, nb, (int)MODE_SYM, 0, INT64_MAX, gi / BT, gi % BT, grp, sum);
+  red[grp * 64 + lr64] = sum[0];
+  red[(kRedGroups + grp) * 64 + lr64] = sum[1];
   __syncthreads();
   if (grp == 0 && gi < N) {
-    float4 r0 = red[lr64], w0 = red[kRedGroups * 64 + lr64];
-#pragma unroll
-    for (int g = 1; g < kRedGroups; ++g) {
-      const float4 o = red[g * 64 + lr64], p = red[(kRedGroups + g) * 64 + lr64];
-      r0.x += o.x; r0.y += o.y; r0.z += o.z;
-      w0.x += p.x; w0.y += p.y; w0.z += p.z;
-    }
-    if (corr) {
-      const float4 o = corr[gi];
-      r0.x += o.x; r0.y += o.y; r0.z += o.z;
-    }
+    float4 r0 = group_sum(red, lr64);
+    if (corr) add3(r0, corr[gi]);
     rw[gi] = r0;
-    rw[(size_t)N + gi] = w0;
+    rw[(size_t)N + gi] = group_sum(red + kRedGroups * 64, lr64);
   }
 }
 
-// Finalize + combine, one launch.  Every block adds the kMomBlocks moment partials in block order
-// (the same bits in every block), forms mse, r, the loss value and the coefficients A, B, C of
-// g_ij = A d_ij + B t_ij + C in fp64, and then gives its 256 rows
+// ---- finalize -------------------------------------------------------------------------------------
+
+// threads < M: the kMomBlocks partials of component threadIdx.x, added in block order
+template <int M>
+__device__ __forceinline__ void sum_moment_partials(const double *__restrict__ mpart, double *dst) {
+  if (threadIdx.x < M) {
+    double s = 0.0;
+    for (int b = 0; b < kMomBlocks; ++b) s += mpart[b * 8 + threadIdx.x];
+    dst[threadIdx.x] = s;
+  }
+}
+
+// What both chains form from the moments s[0..6] = L, sd, sdd, sdt, st, stt, dg: the MSE over all N^2
+// entries, the pair count M, and the covariance and variances of d and t over the pairs (times M).
+// Pearson r = cov / sqrt(vd vt) is left to the callers: the two chains differ in when it is defined.
+struct MomentStats {
+  double mse, M, cov, vd, vt;
+};
+
+__device__ __forceinline__ MomentStats moment_stats(int N, const double *s) {
+  const double n2 = (double)N * (double)N;
+  MomentStats m;
+  m.mse = (2.0 * s[0] + s[6]) / n2;
+  m.M = 0.5 * (double)N * (double)(N - 1);
+  const double sd = s[1], sdd = s[2], sdt = s[3], st = s[4], stt = s[5];
+  m.cov = sdt - sd * st / m.M;
+  m.vd = sdd - sd * sd / m.M;
+  m.vt = stt - st * st / m.M;
+  return m;
+}
+
+// stats[7..10] and loss from the (all-reduced) moments stats[0..6]: mse, pearson r, alpha, total;
+// contrastive: stats[7] = mean_{i<j} |T - D| (fp64, as the reference's float64 truth makes it),
+// stats[8] = NaN, stats[9] = 0.1, stats[10] = total = 0.1 * stats[7].
+__device__ void finalize_stats(int N, int loss_kind, double *__restrict__ stats, float *__restrict__ loss) {
+  if (loss_kind == KIND_CONTRASTIVE) {
+    const double M = 0.5 * (double)N * (double)(N - 1);
+    const double mae = M > 0.0 ? stats[0] / M : 0.0;
+    const double total = 0.1 * mae;
+    stats[7] = mae;
+    stats[8] = NAN;
+    stats[9] = 0.1;
+    stats[10] = total;
+    stats[11] = 0.0;
+    if (loss) loss[0] = (float)total;
+    return;
+  }
+  const MomentStats ms = moment_stats(N, stats);
+  const double mse = ms.mse;
+  // r is reported, never differentiated here (the reference's Pearson term is detached): any positive
+  // pair of variances gives a value.  The moment-dependent chain, which divides its gradient by them,
+  // asks for more (kVarFloor, pairdist_mloss_finalize_kernel).
+  const double r = (ms.vd > 0.0 && ms.vt > 0.0) ? ms.cov / sqrt(ms.vd * ms.vt) : NAN;
+  // HiC_GAT_generalize_directly.py:223-225: alpha from mse_loss.item() (the fp32 value), then
+  // total_loss = mse_loss + alpha*(1-r) evaluated as an fp32 tensor + scalar add.
+  const float msef = (float)mse;
+  const double alpha = fmin(1.0, 0.1 + 1.0 / ((double)msef + 1e-6));
+  const float totalf = msef + (float)(alpha * (1.0 - r));
+  stats[7] = mse;
+  stats[8] = r;
+  stats[9] = alpha;
+  stats[10] = (double)totalf;
+  stats[11] = 0.0;
+  if (loss) loss[0] = loss_kind == 1 ? totalf : msef;
+}
+
+__global__ __launch_bounds__(64) void finalize_kernel(int N, int loss_kind, double *__restrict__ stats,
+                                                      float *__restrict__ loss) {
+  if (threadIdx.x == 0) finalize_stats(N, loss_kind, stats, loss);
+}
+
+__global__ __launch_bounds__(64) void moments_finalize_kernel(const double *__restrict__ part, int N, int loss_kind,
+                                                              double *__restrict__ stats, float *__restrict__ loss) {
+  sum_moment_partials<7>(part, stats);
+  __syncthreads();
+  if (threadIdx.x == 0) finalize_stats(N, loss_kind, stats, loss);
+}
+
+// finalize + a rank's rows of the all-reduced fp64 dcoords narrowed to fp32 (one launch after the
+// multi-GPU loss all-reduce instead of two); with cbuf, also the coordinates in global row order,
+// cglob[i] = cbuf[gidx[i]] (the padded all-gather layout reordered: step()'s return value, no launch
+// of its own)
+__global__ __launch_bounds__(256) void finalize_rows_kernel(int N, int loss_kind, double *__restrict__ stats,
+                                                            float *__restrict__ loss, const double *__restrict__ dc64,
+                                                            int64_t n3, float *__restrict__ dcoords,
+                                                            const float *__restrict__ cbuf,
+                                                            const int32_t *__restrict__ gidx, float *__restrict__ cglob) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t == 0) finalize_stats(N, loss_kind, stats, loss);
+  if (t < n3) dcoords[t] = (float)dc64[t];
+  if (cbuf && t < 3 * (int64_t)N) {
+    const int64_t i = t / 3;
+    cglob[t] = cbuf[3 * (int64_t)gidx[i] + (t - 3 * i)];
+  }
+}
+
+// Finalize + combine of the moment-dependent chain, one launch.  Every block adds the kMomBlocks moment
+// partials in block order (the same bits in every block), forms mse, r, the loss value and the
+// coefficients A, B, C of g_ij = A d_ij + B t_ij + C in fp64, and then gives its 256 rows
 //   dcoords[i] = float(-B R_i + (A + B) (N c_i - sum_j c_j) + C W_i).
 // Block 0 writes stats[0..11] and loss.  stats: 0..6 the moments as hicgat_pairdist_mse_fused,
 // 7 mse, 8 pearson r (NaN when a variance is <= 0), 9 alpha (PEARSON) / 0 (RMSE) / mean of D - T over
@@ -1163,25 +1148,19 @@ __global__ __launch_bounds__(256) void pairdist_mloss_finalize_kernel(const doub
   __shared__ double sm[8];
   __shared__ double coef[3];
   const int tid = threadIdx.x;
-  if (tid < 8) {
-    double s = 0.0;
-    for (int b = 0; b < kMomBlocks; ++b) s += mpart[b * 8 + tid];
-    sm[tid] = s;
-  }
+  sum_moment_partials<8>(mpart, sm);
   __syncthreads();
   if (tid == 0) {
-    const double n2 = (double)N * (double)N, M = 0.5 * (double)N * (double)(N - 1);
-    const double s0 = sm[0], sd = sm[1], sdd = sm[2], sdt = sm[3], st = sm[4], stt = sm[5], dg = sm[6];
+    const MomentStats ms = moment_stats(N, sm);
+    const double n2 = (double)N * (double)N, M = ms.M;
+    const double sd = sm[1], sdd = sm[2], st = sm[4], stt = sm[5];
     const double sdiag = sm[7] + csum[3];
-    const double mse = (2.0 * s0 + dg) / n2;
-    double r = NAN, vd = 0.0, vt = 0.0;
-    if (M > 0.0) {
-      vd = sdd - sd * sd / M;
-      vt = stt - st * st / M;
-      // the tile sums are fp32 per thread: a variance below 2^-20 of the mean square is their rounding
-      // (N = 2: fl(d^2) - d^2), not a spread, and counts as <= 0
-      if (vd > kVarFloor * sdd && vt > kVarFloor * stt) r = (sdt - sd * st / M) / sqrt(vd * vt);
-    }
+    const double mse = ms.mse, vd = ms.vd, vt = ms.vt;
+    // unlike finalize_stats, r feeds the gradient here (1 / vd, 1 / sqrt(vd vt)): the tile sums are fp32
+    // per thread, so a variance below 2^-20 of the mean square is their rounding (N = 2: fl(d^2) - d^2),
+    // not a spread, and counts as <= 0
+    double r = NAN;
+    if (M > 0.0 && vd > kVarFloor * sdd && vt > kVarFloor * stt) r = ms.cov / sqrt(vd * vt);
     const double g4 = 4.0 / n2;
     const double rmse = sqrt(mse + 1e-12);
     const double ebar = (2.0 * (sd - st) - sdiag) / n2;   // the all-entries mean of D - T
@@ -1241,6 +1220,8 @@ __global__ __launch_bounds__(256) void pairdist_mloss_finalize_kernel(const doub
 
 using namespace hicgat;
 
+// ---- host: workspace layout -----------------------------------------------------------------------
+
 constexpr size_t kTileLds = (size_t)BT * BT * sizeof(float);  // LDS image of one T tile
 
 // mode: HICGAT_PD_TRI (1) = the upper-triangle tiling of the fused loss, HICGAT_PD_SQUARE (0) =
@@ -1251,9 +1232,59 @@ extern "C" int64_t hicgat_pairdist_num_tiles(int N, int mode) {
   return mode == HICGAT_PD_TRI ? nb * (nb + 1) / 2 : nb * nb;
 }
 
-// per tile: a (1 + ncol) x 128 float4 partial slab and ncol x 8 fp64 moments (ncol = 1: one column
-// slab per tile)
-static int pd_ncol(int) { return 1; }
+static int64_t pd_support_blocks(int N) { return (N + 3) / 4; }   // support_block: 4 rows (waves) per block
+
+// Byte offsets of a chain's workspace, in this order: [tiles][slabs][128] float4 partial slabs | one
+// 8-double moment record per tile and (support) per support block: tiles [tile_begin, tile_end) at
+// their tile index, the support blocks right after tile_end, so a share's records are one contiguous
+// run that never passes tiles + pd_support_blocks(N) | kMomBlocks moment partials | mloss: csum[4]
+// doubles, rw [2][N] float4 | support: corr [N] float4, the float4 coordinates cpad [N] | 256 spare.
+// The size queries return total; the entry points carve with the same offsets.
+struct PdLayout {
+  size_t part, mom, mpart, csum, rw, corr, cpad, total;
+};
+
+static PdLayout pd_layout(int N, int mode, int slabs, bool support, bool mloss) {
+  const size_t tiles = (size_t)hicgat_pairdist_num_tiles(N, mode), n = N > 0 ? (size_t)N : 0;
+  const size_t f4 = sizeof(float4), rec = 8 * sizeof(double);
+  size_t end = 0;
+  const auto take = [&end](size_t bytes) {
+    const size_t at = end;
+    end += bytes;
+    return at;
+  };
+  PdLayout L;
+  L.part = take(tiles * slabs * BT * f4);
+  L.mom = take((tiles + (support ? (size_t)pd_support_blocks((int)n) : 0)) * rec);
+  L.mpart = take(kMomBlocks * rec);
+  L.csum = take(mloss ? 4 * sizeof(double) : 0);
+  L.rw = take(mloss ? 2 * n * f4 : 0);
+  L.corr = take(support ? n * f4 : 0);
+  L.cpad = take(support ? n * f4 : 0);
+  L.total = end + 256;
+  return L;
+}
+
+static PdLayout fused_layout(int N, int mode, bool support) { return pd_layout(N, mode, 2, support, false); }
+static PdLayout mloss_layout(int N, bool support) { return pd_layout(N, HICGAT_PD_TRI, 4, support, true); }
+
+template <class T>
+static T *ws_at(void *ws, size_t offset) {
+  return reinterpret_cast<T *>(static_cast<char *>(ws) + offset);
+}
+
+extern "C" size_t hicgat_pairdist_workspace_bytes(int N, int mode) { return fused_layout(N, mode, false).total; }
+extern "C" size_t hicgat_pairdist_support_workspace_bytes(int N) {
+  return N <= 0 ? 256 : fused_layout(N, HICGAT_PD_TRI, true).total;
+}
+extern "C" size_t hicgat_pairdist_moment_loss_workspace_bytes(int N) {
+  return N <= 0 ? 256 : mloss_layout(N, false).total;
+}
+extern "C" size_t hicgat_pairdist_moment_loss_support_workspace_bytes(int N) {
+  return N <= 0 ? 256 : mloss_layout(N, true).total;
+}
+
+// ---- host: entry points ---------------------------------------------------------------------------
 
 // the per-pair gradient factor the reduction applies: MSE over N^2 entries of the symmetric D
 // (each pair twice, d(d - t)^2 = 2 (d - t)): 4 / N^2; contrastive: 0.1 / M, M = N (N - 1) / 2 pairs --
@@ -1261,13 +1292,6 @@ static int pd_ncol(int) { return 1; }
 static float loss_scale(int N, int loss_kind) {
   if (loss_kind == KIND_CONTRASTIVE) return N > 1 ? (float)(0.1 / (0.5 * (double)N * (double)(N - 1))) : 0.f;
   return (float)(4.0 / ((double)N * (double)N));
-}
-
-extern "C" size_t hicgat_pairdist_workspace_bytes(int N, int mode) {
-  const int64_t tiles = hicgat_pairdist_num_tiles(N, mode);
-  const int nc = pd_ncol(mode);
-  return (size_t)tiles * ((1 + nc) * BT * sizeof(float4) + nc * 8 * sizeof(double)) + kMomBlocks * 8 * sizeof(double) +
-         256;
 }
 
 // Host twin of tri_decode (exact integer search): tile-row of upper-triangle tile t.
@@ -1280,11 +1304,30 @@ static int tri_row_host(int64_t t, int nb) {
   return lo;
 }
 
-static void carve(void *ws, int64_t tiles, int ncol, float4 **part, double **mom) {
-  char *p = static_cast<char *>(ws);
-  *part = reinterpret_cast<float4 *>(p);
-  *mom = reinterpret_cast<double *>(p + (size_t)tiles * (1 + ncol) * BT * sizeof(float4));
+// A [begin, end) argument (tiles, support rows): end < 0 or past limit means limit, begin < 0 means 0;
+// false when the range is inverted.
+static bool clamp_range(int64_t &begin, int64_t &end, int64_t limit) {
+  if (end < 0 || end > limit) end = limit;
+  if (begin < 0) begin = 0;
+  return begin <= end;
 }
+
+// T (or G) can be read as 16-byte rows of whole tiles: the LDS image of pairdist_tile_kernel<VEC>, the
+// float4 loads of mloss_rows.  col0: the column of the truth that T's first column holds.
+static bool t_is_vec(const float *T, int64_t ld, int64_t col0, int nb) {
+  return (ld % 4 == 0) && (col0 % 4 == 0) && ((reinterpret_cast<uintptr_t>(T) & 15) == 0) &&
+         ld >= (int64_t)nb * BT - col0;
+}
+
+// f(std::integral_constant<int, KIND>) for the runtime loss kind
+template <class F>
+static void with_kind(int loss_kind, F &&f) {
+  if (loss_kind == KIND_COMBINED) f(std::integral_constant<int, KIND_COMBINED>{});
+  else if (loss_kind == KIND_CONTRASTIVE) f(std::integral_constant<int, KIND_CONTRASTIVE>{});
+  else f(std::integral_constant<int, KIND_MSE>{});
+}
+
+static bool loss_kind_ok(int k) { return k >= KIND_MSE && k <= KIND_CONTRASTIVE; }
 
 extern "C" int hicgat_pairdist_fwd(const float *coords, int N, float *D, int64_t ldd,
                                    hicgat_stream_t stream) {
@@ -1303,15 +1346,13 @@ extern "C" int hicgat_pairdist_bwd(const float *coords, const float *G, int N, i
   if (N < 0 || ldg < N) return HICGAT_EINVAL;
   if (N == 0) return HICGAT_OK;
   if (!coords || !G || !dcoords || !workspace) return HICGAT_EINVAL;
-  if (workspace_bytes < hicgat_pairdist_workspace_bytes(N, HICGAT_PD_SQUARE)) return HICGAT_EINVAL;
+  const PdLayout L = fused_layout(N, HICGAT_PD_SQUARE, false);
+  if (workspace_bytes < L.total) return HICGAT_EINVAL;
   const int nb = pd_nb(N);
   const int64_t tiles = (int64_t)nb * nb;
-  float4 *part;
-  double *mom;
-  carve(workspace, tiles, 1, &part, &mom);
-  const bool vec = (ldg % 4 == 0) && ((reinterpret_cast<uintptr_t>(G) & 15) == 0) &&
-                   ldg >= (int64_t)nb * BT;
-  if (vec)
+  float4 *part = ws_at<float4>(workspace, L.part);
+  double *mom = ws_at<double>(workspace, L.mom);
+  if (t_is_vec(G, ldg, 0, nb))
     hipLaunchKernelGGL((pairdist_tile_kernel<MODE_FULL, true, KIND_MSE>), dim3(tiles), dim3(256), kTileLds,
                        (hipStream_t)stream, coords, G, N, ldg, (int64_t)0, (int64_t)0, nb, (int64_t)0, part, mom, 0.f);
   else
@@ -1319,7 +1360,7 @@ extern "C" int hicgat_pairdist_bwd(const float *coords, const float *G, int N, i
                        (hipStream_t)stream, coords, G, N, ldg, (int64_t)0, (int64_t)0, nb, (int64_t)0, part, mom, 0.f);
   HICGAT_CHECK_LAUNCH();
   hipLaunchKernelGGL(pairdist_reduce_kernel, dim3((N + 63) / 64), dim3(1024), 0,
-                     (hipStream_t)stream, part, 1, N, nb, (int)MODE_FULL, (int64_t)0, tiles, 1.0f,
+                     (hipStream_t)stream, part, N, nb, (int)MODE_FULL, (int64_t)0, tiles, 1.0f,
                      dcoords, nullptr, (int64_t)0, (int64_t)0, 0, nullptr, nullptr, 0, 0, nullptr);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
@@ -1330,15 +1371,13 @@ extern "C" int hicgat_pairdist_mse_fused(const float *coords, const float *T, in
                                          int64_t tile_begin, int64_t tile_end, int loss_kind,
                                          double *stats, float *loss, float *dcoords, void *workspace,
                                          size_t workspace_bytes, hicgat_stream_t stream) {
-  if (N < 0 || loss_kind < KIND_MSE || loss_kind > KIND_CONTRASTIVE) return HICGAT_EINVAL;
+  if (N < 0 || !loss_kind_ok(loss_kind)) return HICGAT_EINVAL;
   if (N == 0) return HICGAT_OK;
   if (!coords || !T || !stats || !workspace) return HICGAT_EINVAL;
-  if (workspace_bytes < hicgat_pairdist_workspace_bytes(N, HICGAT_PD_TRI)) return HICGAT_EINVAL;
+  const PdLayout L = fused_layout(N, HICGAT_PD_TRI, false);
+  if (workspace_bytes < L.total) return HICGAT_EINVAL;
   const int nb = pd_nb(N);
-  const int64_t tiles = (int64_t)nb * (nb + 1) / 2;
-  if (tile_end < 0 || tile_end > tiles) tile_end = tiles;
-  if (tile_begin < 0) tile_begin = 0;
-  if (tile_begin > tile_end) return HICGAT_EINVAL;
+  if (!clamp_range(tile_begin, tile_end, hicgat_pairdist_num_tiles(N, HICGAT_PD_TRI))) return HICGAT_EINVAL;
   const int64_t nt = tile_end - tile_begin;
   if (nt > 0) {
     // the band must hold every row / column the tile range reads: rows of tile-rows I0..I1 and
@@ -1349,75 +1388,48 @@ extern "C" int hicgat_pairdist_mse_fused(const float *coords, const float *T, in
         ldt < (int64_t)N - t_col0)
       return HICGAT_EINVAL;
   }
-  float4 *part;
-  double *mom;
-  carve(workspace, tiles, 1, &part, &mom);
-  const bool vec = (ldt % 4 == 0) && (t_col0 % 4 == 0) && ((reinterpret_cast<uintptr_t>(T) & 15) == 0) &&
-                   ldt >= (int64_t)nb * BT - t_col0;
+  float4 *part = ws_at<float4>(workspace, L.part);
+  double *mom = ws_at<double>(workspace, L.mom), *mpart = ws_at<double>(workspace, L.mpart);
+  hipStream_t s = (hipStream_t)stream;
   if (nt > 0) {
-    // the Pearson moments only for the combined loss; MSE needs sum (d - t)^2 only
-#define HICGAT_PD_SYM(V, KD)                                                                          \
-  hipLaunchKernelGGL((pairdist_tile_kernel<MODE_SYM, V, KD>), dim3(nt), dim3(256), V ? kTileLds : 0, \
-                     (hipStream_t)stream, coords, T, N, ldt, t_row0, t_col0, nb, tile_begin, part, mom, 0.f)
-#define HICGAT_PD_KINDS(V)                                                  \
-  if (loss_kind == KIND_COMBINED) HICGAT_PD_SYM(V, KIND_COMBINED);          \
-  else if (loss_kind == KIND_CONTRASTIVE) HICGAT_PD_SYM(V, KIND_CONTRASTIVE); \
-  else HICGAT_PD_SYM(V, KIND_MSE)
-    if (vec) {
-      HICGAT_PD_KINDS(true);
-    } else {
-      HICGAT_PD_KINDS(false);
-    }
-#undef HICGAT_PD_KINDS
-#undef HICGAT_PD_SYM
+    const bool vec = t_is_vec(T, ldt, t_col0, nb);
+    with_kind(loss_kind, [&](auto kind_c) {
+      constexpr int KD = decltype(kind_c)::value;
+      if (vec)
+        hipLaunchKernelGGL((pairdist_tile_kernel<MODE_SYM, true, KD>), dim3(nt), dim3(256), kTileLds, s, coords, T, N,
+                           ldt, t_row0, t_col0, nb, tile_begin, part, mom, 0.f);
+      else
+        hipLaunchKernelGGL((pairdist_tile_kernel<MODE_SYM, false, KD>), dim3(nt), dim3(256), 0, s, coords, T, N, ldt,
+                           t_row0, t_col0, nb, tile_begin, part, mom, 0.f);
+    });
     HICGAT_CHECK_LAUNCH();
   }
   // row / column partials -> dcoords (when wanted) and, in the same launch, kMomBlocks blocks of
   // tile-moment partials; then one small launch: partials -> stats[0..6] -> mse / r / alpha / total
   const float scale = loss_scale(N, loss_kind);
   const int row_blocks = dcoords ? (N + 63) / 64 : 0;
-  double *mpart = mom + (size_t)tiles * 8;
-  hipLaunchKernelGGL(pairdist_reduce_kernel, dim3(row_blocks + kMomBlocks), dim3(1024), 0, (hipStream_t)stream, part,
-                     1, N, nb, (int)MODE_SYM, tile_begin, tile_end, scale, dcoords, mom, tile_begin, tile_end,
-                     row_blocks, mpart, nullptr, 0, 0, nullptr);
+  hipLaunchKernelGGL(pairdist_reduce_kernel, dim3(row_blocks + kMomBlocks), dim3(1024), 0, s, part, N, nb,
+                     (int)MODE_SYM, tile_begin, tile_end, scale, dcoords, mom, tile_begin, tile_end, row_blocks, mpart,
+                     nullptr, 0, 0, nullptr);
   HICGAT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(moments_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, mpart, N, loss_kind, stats,
-                     loss);
+  hipLaunchKernelGGL(moments_finalize_kernel, dim3(1), dim3(64), 0, s, mpart, N, loss_kind, stats, loss);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
 }
 
 extern "C" int hicgat_pairdist_finalize(int N, int loss_kind, double *stats, float *loss,
                                         hicgat_stream_t stream) {
-  if (N <= 0 || !stats || loss_kind < KIND_MSE || loss_kind > KIND_CONTRASTIVE) return HICGAT_EINVAL;
+  if (N <= 0 || !stats || !loss_kind_ok(loss_kind)) return HICGAT_EINVAL;
   hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, N, loss_kind,
                      stats, loss);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
 }
 
-// finalize + a rank's rows of the all-reduced fp64 dcoords narrowed to fp32 (one launch after the
-// multi-GPU loss all-reduce instead of two); with cbuf, also the coordinates in global row order,
-// cglob[i] = cbuf[gidx[i]] (the padded all-gather layout reordered: step()'s return value, no launch
-// of its own)
-__global__ __launch_bounds__(256) void finalize_rows_kernel(int N, int loss_kind, double *__restrict__ stats,
-                                                            float *__restrict__ loss, const double *__restrict__ dc64,
-                                                            int64_t n3, float *__restrict__ dcoords,
-                                                            const float *__restrict__ cbuf,
-                                                            const int32_t *__restrict__ gidx, float *__restrict__ cglob) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t == 0) finalize_stats(N, loss_kind, stats, loss);
-  if (t < n3) dcoords[t] = (float)dc64[t];
-  if (cbuf && t < 3 * (int64_t)N) {
-    const int64_t i = t / 3;
-    cglob[t] = cbuf[3 * (int64_t)gidx[i] + (t - 3 * i)];
-  }
-}
-
 extern "C" int hicgat_pairdist_finalize_rows(int N, int loss_kind, double *stats, float *loss, const double *dc64,
                                              int row_begin, int row_end, float *dcoords, const float *cbuf,
                                              const int32_t *gidx, float *cglob, hicgat_stream_t stream) {
-  if (N <= 0 || !stats || loss_kind < KIND_MSE || loss_kind > KIND_CONTRASTIVE) return HICGAT_EINVAL;
+  if (N <= 0 || !stats || !loss_kind_ok(loss_kind)) return HICGAT_EINVAL;
   if (row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
   const int64_t n3 = 3 * (int64_t)(row_end - row_begin);
   if (n3 > 0 && (!dc64 || !dcoords)) return HICGAT_EINVAL;
@@ -1431,67 +1443,41 @@ extern "C" int hicgat_pairdist_finalize_rows(int N, int loss_kind, double *stats
   return HICGAT_OK;
 }
 
-// ---- background form: T = bg except at a sorted symmetric CSR support + the diagonal -----------
-static int64_t pd_support_blocks(int N) { return (N + 3) / 4; }
-
-extern "C" size_t hicgat_pairdist_support_workspace_bytes(int N) {
-  if (N <= 0) return 256;
-  const int64_t tiles = hicgat_pairdist_num_tiles(N, HICGAT_PD_TRI);
-  return (size_t)tiles * 2 * BT * sizeof(float4) + (size_t)(tiles + pd_support_blocks(N)) * 8 * sizeof(double) +
-         kMomBlocks * 8 * sizeof(double) + 2 * (size_t)N * sizeof(float4) + 256;   // corr + the float4 coords
-}
-
+// background form: T = bg except at a sorted symmetric CSR support + the diagonal
 extern "C" int hicgat_pairdist_mse_fused_support(const float *coords, const int32_t *cmap, int N, float background,
                                                  const int32_t *rowptr, const int32_t *col, const float *val,
                                                  const float *diag, int64_t tile_begin, int64_t tile_end,
                                                  int support_row_begin, int support_row_end, int loss_kind,
                                                  double *stats, float *loss, float *dcoords, double *dcoords64,
                                                  void *workspace, size_t workspace_bytes, hicgat_stream_t stream) {
-  if (N < 0 || loss_kind < KIND_MSE || loss_kind > KIND_CONTRASTIVE) return HICGAT_EINVAL;
+  if (N < 0 || !loss_kind_ok(loss_kind)) return HICGAT_EINVAL;
   if (N == 0) return HICGAT_OK;
   if (!coords || !rowptr || !col || !val || !diag || !stats || !workspace) return HICGAT_EINVAL;
-  if (workspace_bytes < hicgat_pairdist_support_workspace_bytes(N)) return HICGAT_EINVAL;
+  const PdLayout L = fused_layout(N, HICGAT_PD_TRI, true);
+  if (workspace_bytes < L.total) return HICGAT_EINVAL;
   const int nb = pd_nb(N);
-  const int64_t tiles = (int64_t)nb * (nb + 1) / 2;
-  if (tile_end < 0 || tile_end > tiles) tile_end = tiles;
-  if (tile_begin < 0) tile_begin = 0;
-  if (tile_begin > tile_end) return HICGAT_EINVAL;
-  if (support_row_end < 0 || support_row_end > N) support_row_end = N;
-  if (support_row_begin < 0) support_row_begin = 0;
-  if (support_row_begin > support_row_end) return HICGAT_EINVAL;
+  const int64_t tiles = hicgat_pairdist_num_tiles(N, HICGAT_PD_TRI);
+  int64_t s0 = support_row_begin, s1 = support_row_end;
+  if (!clamp_range(tile_begin, tile_end, tiles) || !clamp_range(s0, s1, N)) return HICGAT_EINVAL;
   const int64_t nt = tile_end - tile_begin;
-  const int64_t sblocks = (support_row_end - support_row_begin + 3) / 4;
-  char *p = static_cast<char *>(workspace);
-  float4 *part = reinterpret_cast<float4 *>(p);
-  // moment records: tiles [tile_begin, tile_end) at their tile index, the support blocks right
-  // after tile_end (so [tile_begin, tile_end + sblocks) is one contiguous run; the workspace holds
-  // tiles + pd_support_blocks(N) records, and tile_end + sblocks never exceeds that)
-  double *mom = reinterpret_cast<double *>(p + (size_t)tiles * 2 * BT * sizeof(float4));
-  double *mpart = mom + (size_t)(tiles + pd_support_blocks(N)) * 8;
-  float4 *corr = reinterpret_cast<float4 *>(mpart + kMomBlocks * 8);
+  const int64_t sblocks = (s1 - s0 + 3) / 4;
+  float4 *part = ws_at<float4>(workspace, L.part), *corr = ws_at<float4>(workspace, L.corr);
+  double *mom = ws_at<double>(workspace, L.mom), *mpart = ws_at<double>(workspace, L.mpart);
+  double *smom = mom + (size_t)tile_end * 8;   // the support blocks' records (PdLayout)
   hipStream_t s = (hipStream_t)stream;
   // bulk: every pair i < j of the tile range at the background value (no T read); support: the
-  // entries of rows [support_row_begin, support_row_end) that differ, and those rows' diagonal
+  // entries of rows [s0, s1) that differ, and those rows' diagonal
   // a rank's share (dcoords64: the sharded step): the support blocks ride in the tile launch (one
   // launch fewer on the critical path; at N = 20000 on one GPU the support pass needs the occupancy
   // of its own launch: 1.881 / 1.884 vs 1.875 / 1.877 ms per step, profiles/r04u_ab_single_gpu.txt)
   const bool ride = dcoords64 && nt > 0 && sblocks > 0;
   SupportArgs sa;
-  if (ride) {
-    sa.rowptr = rowptr;
-    sa.col = col;
-    sa.val = val;
-    sa.diag = diag;
-    sa.corr = corr;
-    sa.mom = mom + (size_t)tile_end * 8;
-    sa.row_begin = support_row_begin;
-    sa.row_end = support_row_end;
-    sa.ntiles = nt;
-  }
+  if (ride) sa = SupportArgs{rowptr, col, val, diag, corr, smom, (int)s0, (int)s1, nt};
   // the whole triangle in one launch before a separate support launch (one GPU): the diagonal tiles
   // write the float4 copy of the coordinates the support pass gathers (19 -> 8 us at N = 20000)
-  float4 *cpad = (!ride && !cmap && tile_begin == 0 && tile_end == tiles && sblocks > 0) ? corr + N : nullptr;
-  const auto tiles_for = [&](auto kind_c) {
+  float4 *cpad = (!ride && !cmap && tile_begin == 0 && tile_end == tiles && sblocks > 0)
+                     ? ws_at<float4>(workspace, L.cpad) : nullptr;
+  with_kind(loss_kind, [&](auto kind_c) {
     constexpr int KD = decltype(kind_c)::value;
     if (ride)
       hipLaunchKernelGGL((pairdist_tile_kernel<MODE_SYM, false, KD, true, true>), dim3(nt + sblocks), dim3(256), 0, s,
@@ -1502,22 +1488,18 @@ extern "C" int hicgat_pairdist_mse_fused_support(const float *coords, const int3
                          nullptr, N, (int64_t)0, (int64_t)0, (int64_t)0, nb, tile_begin, part, mom, background, cmap,
                          SupportArgs{}, cpad);
     if (sblocks > 0 && !ride)
-      hipLaunchKernelGGL(pairdist_support_kernel<KD>, dim3(sblocks), dim3(256), 0, s, coords, N, background,
-                         support_row_begin, support_row_end, rowptr, col, val, diag, corr, mom + (size_t)tile_end * 8,
-                         cmap, cpad);
-  };
-  if (loss_kind == KIND_COMBINED) tiles_for(std::integral_constant<int, KIND_COMBINED>{});
-  else if (loss_kind == KIND_CONTRASTIVE) tiles_for(std::integral_constant<int, KIND_CONTRASTIVE>{});
-  else tiles_for(std::integral_constant<int, KIND_MSE>{});
+      hipLaunchKernelGGL(pairdist_support_kernel<KD>, dim3(sblocks), dim3(256), 0, s, coords, N, background, (int)s0,
+                         (int)s1, rowptr, col, val, diag, corr, smom, cmap, cpad);
+  });
   HICGAT_CHECK_LAUNCH();
   const float scale = loss_scale(N, loss_kind);
   const int row_blocks = (dcoords || dcoords64) ? (N + 63) / 64 : 0;
   // dcoords64: the caller all-reduces [stats | dcoords64] and finalizes (hicgat_pairdist_finalize_rows),
   // so a small share's moments go straight into stats[0..6] (stats[7..11] and loss are left alone)
   const bool one = dcoords64 && nt + sblocks <= kOneBlockMoments;
-  hipLaunchKernelGGL(pairdist_reduce_kernel, dim3(row_blocks + (one ? 1 : kMomBlocks)), dim3(1024), 0, s, part, 1,
-                     N, nb, (int)MODE_SYM, tile_begin, tile_end, scale, dcoords, mom, tile_begin, tile_end + sblocks,
-                     row_blocks, one ? stats : mpart, corr, support_row_begin, support_row_end, dcoords64);
+  hipLaunchKernelGGL(pairdist_reduce_kernel, dim3(row_blocks + (one ? 1 : kMomBlocks)), dim3(1024), 0, s, part, N, nb,
+                     (int)MODE_SYM, tile_begin, tile_end, scale, dcoords, mom, tile_begin, tile_end + sblocks,
+                     row_blocks, one ? stats : mpart, corr, (int)s0, (int)s1, dcoords64);
   HICGAT_CHECK_LAUNCH();
   if (!one) {
     hipLaunchKernelGGL(moments_finalize_kernel, dim3(1), dim3(64), 0, s, mpart, N, loss_kind, stats, loss);
@@ -1526,39 +1508,23 @@ extern "C" int hicgat_pairdist_mse_fused_support(const float *coords, const int3
   return HICGAT_OK;
 }
 
-// ---- moment-dependent losses: tile pass -> reduce -> finalize + combine ---------------------------
-// workspace: [tiles][4][128] float4 slabs | (tiles + support blocks) moment records | kMomBlocks
-// partials | csum[4] | rw [2][N] float4 | corr [N] float4 | coordinates [N] float4 (the last two:
-// background form)
-static size_t mloss_workspace(int N, bool support) {
-  if (N <= 0) return 256;
-  const int64_t tiles = hicgat_pairdist_num_tiles(N, HICGAT_PD_TRI);
-  size_t b = (size_t)tiles * kMSlabs * BT * sizeof(float4) +
-             (size_t)(tiles + (support ? pd_support_blocks(N) : 0)) * 8 * sizeof(double) +
-             kMomBlocks * 8 * sizeof(double) + 4 * sizeof(double) + 2 * (size_t)N * sizeof(float4);
-  if (support) b += 2 * (size_t)N * sizeof(float4);
-  return b + 256;
-}
-
-extern "C" size_t hicgat_pairdist_moment_loss_workspace_bytes(int N) { return mloss_workspace(N, false); }
-extern "C" size_t hicgat_pairdist_moment_loss_support_workspace_bytes(int N) { return mloss_workspace(N, true); }
-
-// T == NULL: the background form (rowptr / col / val / diag and background)
+// moment-dependent losses: tile pass -> reduce -> finalize + combine.  T == NULL: the background form
+// (rowptr / col / val / diag and background)
 static int mloss_run(const float *coords, const float *T, int64_t ldt, int N, float background, const int32_t *rowptr,
                      const int32_t *col, const float *val, const float *diag, int mloss_kind, double alpha,
-                     double *stats, float *loss, float *dcoords, void *workspace, hipStream_t s) {
+                     double *stats, float *loss, float *dcoords, void *workspace, size_t workspace_bytes,
+                     hipStream_t s) {
   const bool support = T == nullptr;
+  const PdLayout L = mloss_layout(N, support);
+  if (workspace_bytes < L.total) return HICGAT_EINVAL;
   const int nb = pd_nb(N);
-  const int64_t tiles = (int64_t)nb * (nb + 1) / 2;
+  const int64_t tiles = hicgat_pairdist_num_tiles(N, HICGAT_PD_TRI);
   const int64_t sblocks = support ? pd_support_blocks(N) : 0;
-  char *p = static_cast<char *>(workspace);
-  float4 *part = reinterpret_cast<float4 *>(p);
-  double *mom = reinterpret_cast<double *>(p + (size_t)tiles * kMSlabs * BT * sizeof(float4));
-  double *mpart = mom + (size_t)(tiles + sblocks) * 8;
-  double *csum = mpart + kMomBlocks * 8;
-  float4 *rw = reinterpret_cast<float4 *>(csum + 4);
-  float4 *corr = support ? rw + 2 * (size_t)N : nullptr;
-  float4 *cpad = support ? corr + N : nullptr;
+  float4 *part = ws_at<float4>(workspace, L.part), *rw = ws_at<float4>(workspace, L.rw);
+  double *mom = ws_at<double>(workspace, L.mom), *mpart = ws_at<double>(workspace, L.mpart);
+  double *csum = ws_at<double>(workspace, L.csum);
+  float4 *corr = support ? ws_at<float4>(workspace, L.corr) : nullptr;
+  float4 *cpad = support ? ws_at<float4>(workspace, L.cpad) : nullptr;
   if (support) {
     hipLaunchKernelGGL(pairdist_mloss_tile_kernel<true>, dim3(tiles), dim3(256), 0, s, coords, nullptr, N,
                        (int64_t)0, 0, nb, part, mom, background, cpad);
@@ -1568,9 +1534,8 @@ static int mloss_run(const float *coords, const float *T, int64_t ldt, int N, fl
     hipLaunchKernelGGL(pairdist_support_kernel<KIND_COMBINED>, dim3(sblocks), dim3(256), 0, s, coords, N, background,
                        0, N, rowptr, col, val, diag, corr, mom + (size_t)tiles * 8, nullptr, cpad);
   } else {
-    const bool vec = (ldt % 4 == 0) && ((reinterpret_cast<uintptr_t>(T) & 15) == 0) && ldt >= (int64_t)nb * BT;
     hipLaunchKernelGGL(pairdist_mloss_tile_kernel<false>, dim3(tiles), dim3(256), 0, s, coords, T, N, ldt,
-                       vec ? 1 : 0, nb, part, mom, 0.f, nullptr);
+                       t_is_vec(T, ldt, 0, nb) ? 1 : 0, nb, part, mom, 0.f, nullptr);
   }
   HICGAT_CHECK_LAUNCH();
   const int row_blocks = (N + 63) / 64;
@@ -1592,9 +1557,8 @@ extern "C" int hicgat_pairdist_moment_loss(const float *coords, const float *T, 
   if (N < 0 || !mloss_kind_ok(mloss_kind) || !(alpha == alpha)) return HICGAT_EINVAL;
   if (N == 0) return HICGAT_OK;
   if (!coords || !T || !stats || !workspace || ldt < N) return HICGAT_EINVAL;
-  if (workspace_bytes < mloss_workspace(N, false)) return HICGAT_EINVAL;
   return mloss_run(coords, T, ldt, N, 0.f, nullptr, nullptr, nullptr, nullptr, mloss_kind, alpha, stats, loss,
-                   dcoords, workspace, (hipStream_t)stream);
+                   dcoords, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int hicgat_pairdist_moment_loss_support(const float *coords, int N, float background,
@@ -1605,7 +1569,6 @@ extern "C" int hicgat_pairdist_moment_loss_support(const float *coords, int N, f
   if (N < 0 || !mloss_kind_ok(mloss_kind) || !(alpha == alpha)) return HICGAT_EINVAL;
   if (N == 0) return HICGAT_OK;
   if (!coords || !rowptr || !col || !val || !diag || !stats || !workspace) return HICGAT_EINVAL;
-  if (workspace_bytes < mloss_workspace(N, true)) return HICGAT_EINVAL;
   return mloss_run(coords, nullptr, 0, N, background, rowptr, col, val, diag, mloss_kind, alpha, stats, loss, dcoords,
-                   workspace, (hipStream_t)stream);
+                   workspace, workspace_bytes, (hipStream_t)stream);
 }
