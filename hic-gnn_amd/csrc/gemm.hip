@@ -241,36 +241,52 @@ __global__ void colsum_zero_kernel(float *out, int N, int accumulate) {
 // is then [M*N dW partials | M db partials].
 int gemm_wgrad_ring_launch(const float *A, int64_t lda, const float *B, int64_t ldb, int M, int N, int K, int kchunk,
                            int splits, float *slab, int64_t slab_stride, hipStream_t s);   // gemm_wgrad.hip
+bool gemm_wgrad_ring_fits(const void *A, int64_t lda, const void *B, int64_t ldb, int M, int N, int K, int splits);
 
-// ring (K-major A and B, 128 x 128 tiles, K split, no db): the partial slabs from the LDS-DMA ring
-// kernel of gemm_wgrad.hip when the problem fits it -- the same kchunk, slabs and slab sum, bit-identical
-// partials -- else from gemm_kernel as before.
+// ---- the form of a launch: every decision between kernels and between gemm_tile's template forms is
+// taken by the predicates from here to form_for (below tile_for); launch<>, dispatch<>,
+// hicgat_gemm_wgrad, the per-job `vec` of the two grouped launches and hicgat_gemm_form all ask them.
+enum GemmKernel { kGemmKernel = HICGAT_GEMM_FORM_GEMM_KERNEL, kGemmTall = HICGAT_GEMM_FORM_TALL,
+                  kGemmRing = HICGAT_GEMM_FORM_RING };
+struct GemmForm {
+  GemmKernel kernel;
+  int bm, bn;          // the tile (160 x 128 for the tall kernel)
+  bool vec, db, cs;    // gemm_tile's VEC, DB and CS
+};
+
+// float4 staging needs every float4 inside its operand row, 16-B aligned rows and 16-B aligned operands
+static bool stage4_ok(bool a_km, bool b_km, int M, int N, int K, const void *A, int64_t lda, const void *B,
+                      int64_t ldb) {
+  const bool a_ok = a_km ? (M % 4 == 0 && lda % 4 == 0) : (K % 4 == 0 && lda % 4 == 0);
+  const bool b_ok = b_km ? (N % 4 == 0 && ldb % 4 == 0) : (K % 4 == 0 && ldb % 4 == 0);
+  const bool al = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
+  return a_ok && b_ok && al;
+}
+// double-buffered LDS with float4 staging: the dX layout only (every layout measured: no gain elsewhere)
+constexpr bool stage_db(bool a_km, bool b_km) { return !a_km && b_km; }
+
+// f.kernel == kGemmRing (K-major A and B, 128 x 128 tiles, K split, no db): the partial slabs from the
+// LDS-DMA ring kernel of gemm_wgrad.hip -- the same kchunk, slabs and slab sum, bit-identical partials --
+// else from gemm_kernel in the form f names.
 template <int BM, int BN, bool AK, bool BK_>
-static int launch(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc, int M, int N,
-                  int K, int splits, const float *bias, float *slab, int acc, hipStream_t s, float *csum = nullptr,
-                  bool ring = false) {
+static int launch(const GemmForm &f, const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
+                  int M, int N, int K, int splits, const float *bias, float *slab, int acc, hipStream_t s,
+                  float *csum = nullptr) {
   const int kchunk = ((K + splits - 1) / splits + GK - 1) / GK * GK;
   const dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN, splits);
-  // float4 staging needs every float4 inside its operand row and 16-B aligned rows
-  const bool a_ok = AK ? (M % 4 == 0 && lda % 4 == 0) : (K % 4 == 0 && lda % 4 == 0);
-  const bool b_ok = BK_ ? (N % 4 == 0 && ldb % 4 == 0) : (K % 4 == 0 && ldb % 4 == 0);
-  const bool al = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
-  const bool cs = AK && csum != nullptr;
+  const bool cs = f.cs;
   const int64_t stride = (int64_t)M * N + (cs ? M : 0);
   float *sl = splits > 1 ? slab : nullptr;
   float *cdst = cs ? (sl ? slab + (int64_t)M * N : csum) : nullptr;
 #define HICGAT_GEMM_GO(V, D, C_)                                                                            \
   hipLaunchKernelGGL((gemm_kernel<BM, BN, AK, BK_, V, D, C_>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N, \
                      K, kchunk, bias, sl, stride, acc, cdst)
-  int ring_rc = HICGAT_EUNSUPPORTED;
-  if (ring && AK && BK_ && BM == 128 && BN == 128 && sl && !cs)
-    ring_rc = gemm_wgrad_ring_launch(A, lda, B, ldb, M, N, K, kchunk, splits, sl, stride, s);
-  if (ring_rc == HICGAT_OK) {
-    // the slabs are written; the slab sum below finishes C
-  } else if (ring_rc != HICGAT_EUNSUPPORTED) {
-    return ring_rc;
-  } else if (a_ok && b_ok && al) {
-    constexpr bool db = !AK && BK_;   // double-buffered LDS: the dX layout (every layout measured: no gain)
+  if (f.kernel == kGemmRing) {
+    // the slabs are written here; the slab sum below finishes C
+    const int rc = gemm_wgrad_ring_launch(A, lda, B, ldb, M, N, K, kchunk, splits, sl, stride, s);
+    if (rc != HICGAT_OK) return rc;
+  } else if (f.vec) {
+    constexpr bool db = stage_db(AK, BK_);
     if (cs) HICGAT_GEMM_GO(true, db, AK);
     else HICGAT_GEMM_GO(true, db, false);
   } else {
@@ -289,6 +305,7 @@ static int launch(const float *A, int64_t lda, const float *B, int64_t ldb, floa
 
 int gemm_tall_launch(bool b_kmajor, const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
                      int M, int N, int K, const float *bias, int accumulate, hipStream_t s);   // gemm_tall.hip
+bool gemm_tall_fits(const void *A, int64_t lda, const void *B, int64_t ldb, int M, int N, int K);
 
 // Problems with fewer 160x128 tiles than this go to the 64x128 kernel (2.5x the workgroups): one
 // workgroup per tile with the whole K inside, the tall kernel needs ~one tile per CU -- a rank's
@@ -312,7 +329,8 @@ struct GemmTile {
 // and 256 x 128 tiles for the tall problems measured slower, round 1); 64 x 64 below 128 columns.
 static GemmTile rows_tile(int N) { return N >= 128 ? GemmTile{false, 64, 128} : GemmTile{false, 64, 64}; }
 
-// The one tile rule: dispatch<>, hicgat_gemm_wgrad and the split queries below all ask here.
+// The one tile rule: form_for (dispatch<>, hicgat_gemm_wgrad, hicgat_gemm_form) and the split queries
+// below all ask here.
 static GemmTile tile_for(bool a_kmajor, int M, int N, int splits) {
   // tall node-row problems (Linear forward, input gradient): the 160x128 LDS-DMA kernel (gemm_tall.hip)
   const bool tall = !a_kmajor && splits == 1 && M >= kTallMinM &&
@@ -323,23 +341,40 @@ static GemmTile tile_for(bool a_kmajor, int M, int N, int splits) {
   return t;
 }
 
+// The form of a hicgat_gemm call (with_db = false) or of a hicgat_gemm_wgrad call (K-major layout,
+// impl = HICGAT_GEMM_F32, with_db = db given).  Addresses: alignment only.
+static GemmForm form_for(bool a_km, bool b_km, int M, int N, int K, const void *A, int64_t lda, const void *B,
+                         int64_t ldb, int splits, int impl, bool with_db) {
+  const GemmTile t = tile_for(a_km, M, N, splits);
+  // the tall kernel when the problem fits its tiling, else the tile below
+  if (t.tall && gemm_tall_fits(A, lda, B, ldb, M, N, K)) return GemmForm{kGemmTall, kTallBM, kTallBN, true, false, false};
+  const bool cs = a_km && with_db;
+  // A K-split weight gradient of whole 128 x 128 tiles (lin_l's dW after the gather) takes the
+  // LDS-DMA ring kernel (gemm_wgrad.hip); impl = HICGAT_GEMM_F32 keeps gemm_kernel (A/B, bitwise test),
+  // and so does the bias-gradient form (the ring kernel has no column sums)
+  if (t.bm == 128 && a_km && b_km && impl == HICGAT_GEMM_AUTO && splits > 1 && !cs &&
+      gemm_wgrad_ring_fits(A, lda, B, ldb, M, N, K, splits))
+    return GemmForm{kGemmRing, 128, 128, true, false, false};
+  const bool vec = stage4_ok(a_km, b_km, M, N, K, A, lda, B, ldb);
+  return GemmForm{kGemmKernel, t.bm, t.bn, vec, vec && stage_db(a_km, b_km), cs};
+}
+
+// gemm_kernel (or the ring kernel) on the tile f names
+template <bool AK, bool BK_>
+static int launch_tile(const GemmForm &f, const float *A, int64_t lda, const float *B, int64_t ldb, float *C,
+                       int64_t ldc, int M, int N, int K, int splits, const float *bias, float *slab, int acc,
+                       hipStream_t s, float *csum = nullptr) {
+  if (f.bm == 128) return launch<128, 128, AK, BK_>(f, A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s, csum);
+  if (f.bn == 128) return launch<64, 128, AK, BK_>(f, A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s, csum);
+  return launch<64, 64, AK, BK_>(f, A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s, csum);
+}
+
 template <bool AK, bool BK_>
 static int dispatch(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc, int M, int N,
                     int K, int splits, const float *bias, float *slab, int acc, int impl, hipStream_t s) {
-  const GemmTile t = tile_for(AK, M, N, splits);
-  if (t.tall) {
-    const int rc = gemm_tall_launch(BK_, A, lda, B, ldb, C, ldc, M, N, K, bias, acc, s);
-    if (rc != HICGAT_EUNSUPPORTED) return rc;
-  }
-  // A K-split weight gradient of whole 128 x 128 tiles (lin_l's dW after the gather) takes the
-  // LDS-DMA ring kernel (gemm_wgrad.hip); impl = HICGAT_GEMM_F32 keeps gemm_kernel (A/B, bitwise test)
-  if (t.bm == 128) {
-    const bool ring = AK && BK_ && impl == HICGAT_GEMM_AUTO && splits > 1 && M % 128 == 0 && N % 128 == 0 &&
-                      N <= 1024 && lda % 4 == 0 && ldb % 4 == 0;
-    return launch<128, 128, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s, nullptr, ring);
-  }
-  if (t.bn == 128) return launch<64, 128, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
-  return launch<64, 64, AK, BK_>(A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
+  const GemmForm f = form_for(AK, BK_, M, N, K, A, lda, B, ldb, splits, impl, false);
+  if (f.kernel == kGemmTall) return gemm_tall_launch(BK_, A, lda, B, ldb, C, ldc, M, N, K, bias, acc, s);
+  return launch_tile<AK, BK_>(f, A, lda, B, ldb, C, ldc, M, N, K, splits, bias, slab, acc, s);
 }
 
 // ---- grouped parameter gradients (hicgat_param_grads_grouped) -------------------------------------
@@ -543,7 +578,7 @@ __global__ __launch_bounds__(256, kOcc64) void gemm_rows_grouped_kernel(const RJ
   const int bz = local / per, rem = local - bz * per, bx = rem % J.tm, by = rem / J.tm;
   // splits = 1: the tile writes C (+ bias, + relu copy) itself and no reduce launch follows
   const bool direct = jobs.splits == 1;
-  gemm_tile<kRowsBM, kRowsBN, false, B_KM, true, !B_KM ? false : true, false>(
+  gemm_tile<kRowsBM, kRowsBN, false, B_KM, true, stage_db(false, B_KM), false>(
       J.a, J.lda, J.b, J.ldb, J.c, J.ldc, J.M, J.N, J.K, J.kchunk, direct ? J.bias : nullptr,
       direct ? nullptr : J.slab, (int64_t)J.M * J.N, 0, nullptr, bx, by, bz, direct ? J.cr : nullptr, J.ldr);
 }
@@ -606,11 +641,12 @@ extern "C" int hicgat_gemm_rows_grouped(const hicgat_gemm_job *jobs, int n, int 
   for (int i = 0; i < n; ++i) {
     const hicgat_gemm_job &a = jobs[i];
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || !a.a || !a.b || !a.c) return HICGAT_EINVAL;
-    // float4 staging and float4 epilogue: every row a multiple of 4 floats, 16-B aligned
-    const bool ok = a.K % 4 == 0 && a.lda % 4 == 0 && a.ldb % 4 == 0 && a.N % 4 == 0 && a.ldc % 4 == 0 &&
-                    (!a.c_relu || a.ldr % 4 == 0) &&
-                    ((reinterpret_cast<uintptr_t>(a.a) | reinterpret_cast<uintptr_t>(a.b) | reinterpret_cast<uintptr_t>(a.c) |
-                      reinterpret_cast<uintptr_t>(a.c_relu) | reinterpret_cast<uintptr_t>(a.bias)) & 15) == 0;
+    // float4 staging (the kernel has no scalar form) and float4 epilogue: every row a multiple of 4
+    // floats, 16-B aligned
+    const bool ok = stage4_ok(false, b_kmajor != 0, a.M, a.N, a.K, a.a, a.lda, a.b, a.ldb) && a.N % 4 == 0 &&
+                    a.ldc % 4 == 0 && (!a.c_relu || a.ldr % 4 == 0) &&
+                    ((reinterpret_cast<uintptr_t>(a.c) | reinterpret_cast<uintptr_t>(a.c_relu) |
+                      reinterpret_cast<uintptr_t>(a.bias)) & 15) == 0;
     if (!ok) return HICGAT_EUNSUPPORTED;
     RJob &J = rj.j[rj.n++];
     J.a = a.a;
@@ -722,12 +758,13 @@ extern "C" int hicgat_param_grads_grouped(const hicgat_wgrad_job *w, int nw, con
     J.M = a.M;
     J.N = a.N;
     J.K = a.K;
-    J.kchunk = kc;
+    // the common chunk depth for a split job; a job that is not split (lddw > N) is ONE chunk of its
+    // whole K (with kc it summed rows [0, kc) only whenever the launch's chunks were shorter than its K)
+    J.kchunk = (a.K > 0 && splits[i] > 1) ? kc : std::max(kc, (a.K + GK - 1) / GK * GK);
     J.tm = (a.M + kGroupTile - 1) / kGroupTile;
     J.tn = (a.N + kGroupTile - 1) / kGroupTile;
     J.accumulate = a.accumulate;
-    J.vec = (a.M % 4 == 0 && a.ldy % 4 == 0 && a.N % 4 == 0 && a.ldx % 4 == 0 &&
-             ((reinterpret_cast<uintptr_t>(a.dy) | reinterpret_cast<uintptr_t>(a.x)) & 15) == 0);
+    J.vec = stage4_ok(true, true, a.M, a.N, a.K, a.dy, a.ldy, a.x, a.ldx);
     const int sp = a.K > 0 ? splits[i] : 1;
     J.slab = nullptr;
     if (sp > 1) {
@@ -786,6 +823,24 @@ extern "C" int hicgat_gemm_row_splits(int M, int N, int K) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(K / kSplitMinDepth, (kTarget + wgs - 1) / wgs));
 }
 
+// The form hicgat_gemm / hicgat_gemm_wgrad launch for these arguments: form_for, as the dispatch asks it.
+extern "C" int hicgat_gemm_form(int a_kmajor, int b_kmajor, int M, int N, int K, const void *A, int64_t lda,
+                                const void *B, int64_t ldb, int splits, int impl, int with_db) {
+  if (impl == HICGAT_GEMM_X3) return HICGAT_EUNSUPPORTED;
+  if (impl != HICGAT_GEMM_AUTO && impl != HICGAT_GEMM_F32) return HICGAT_EINVAL;
+  if (M < 0 || N < 0 || K < 0 || splits < 1) return HICGAT_EINVAL;
+  if (with_db && !(a_kmajor && b_kmajor)) return HICGAT_EINVAL;
+  if (M == 0 || N == 0) return HICGAT_GEMM_FORM_NONE;
+  if (!A || !B) return HICGAT_EINVAL;
+  const GemmForm f = form_for(a_kmajor != 0, b_kmajor != 0, M, N, K, A, lda, B, ldb, splits, impl, with_db != 0);
+  const int tile = f.bm == kTallBM ? HICGAT_GEMM_FORM_160x128
+                   : f.bm == 128   ? HICGAT_GEMM_FORM_128x128
+                   : f.bn == 128   ? HICGAT_GEMM_FORM_64x128
+                                   : HICGAT_GEMM_FORM_64x64;
+  return (int)f.kernel | tile | (f.vec ? HICGAT_GEMM_FORM_VEC : 0) | (f.db ? HICGAT_GEMM_FORM_DB : 0) |
+         (f.cs ? HICGAT_GEMM_FORM_CS : 0);
+}
+
 // K-split of a weight-gradient GEMM whose K is the node count: about target_wgs workgroups, each
 // split at least 256 rows deep.  The tiles are counted by a rule of its own, kept as it is because
 // the targets were measured with it: tile_for's row height without its M <= 1024 bound (M > 1024
@@ -837,11 +892,9 @@ extern "C" int hicgat_gemm_wgrad(int M, int N, int K, const float *dY, int64_t l
     return HICGAT_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   float *slab = static_cast<float *>(workspace);
-  const GemmTile t = tile_for(true, M, N, splits);
-  if (t.bm == 128)
-    return launch<128, 128, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
-  if (t.bn == 128) return launch<64, 128, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
-  return launch<64, 64, true, true>(dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
+  // always gemm_kernel (impl F32): the ring kernel has no bias-gradient column sums
+  const GemmForm f = form_for(true, true, M, N, K, dY, ldy, X, ldx, splits, HICGAT_GEMM_F32, db != nullptr);
+  return launch_tile<true, true>(f, dY, ldy, X, ldx, dW, lddw, M, N, K, splits, nullptr, slab, accumulate, s, db);
 }
 
 extern "C" size_t hicgat_colsum_workspace_bytes(int K, int N) { return colsum_workspace_bytes(K, N); }

@@ -180,14 +180,21 @@ __global__ __launch_bounds__(256, 2) void gemm_tall_kernel(const float *__restri
   }
 }
 
+// Whether the problem fits the tall kernel's tiling (whole 128-column tiles and 16-deep stages, rows
+// and operands the 16-byte LDS-DMA copies can read): the one statement of it, asked by the dispatch
+// of gemm.hip (and its hicgat_gemm_form) and by the launch below.  Addresses: alignment only.
+bool gemm_tall_fits(const void *A, int64_t lda, const void *B, int64_t ldb, int M, int N, int K) {
+  const bool al = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
+  if (!al || M < TBM || N % TBN || K % TBK || K < TBK || lda % 4 || ldb % 4) return false;
+  return (int64_t)((M + TBM - 1) / TBM) * (N / TBN) <= 0x7fffffff;
+}
+
 // The tall kernel takes the problem when it fits its tiling: returns HICGAT_EUNSUPPORTED otherwise
 // (the caller then uses the 64x128 kernel of gemm.hip).
 int gemm_tall_launch(bool b_kmajor, const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
                      int M, int N, int K, const float *bias, int accumulate, hipStream_t s) {
-  const bool al = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
-  if (!al || M < TBM || N % TBN || K % TBK || K < TBK || lda % 4 || ldb % 4) return HICGAT_EUNSUPPORTED;
+  if (!gemm_tall_fits(A, lda, B, ldb, M, N, K)) return HICGAT_EUNSUPPORTED;
   const int64_t tiles = (int64_t)((M + TBM - 1) / TBM) * (N / TBN);
-  if (tiles > 0x7fffffff) return HICGAT_EUNSUPPORTED;
   if (b_kmajor)
     hipLaunchKernelGGL(gemm_tall_kernel<false>, dim3((unsigned)tiles), dim3(256), kTallLds, s, A, lda, B, ldb, C, ldc, M,
                        N, K, bias, accumulate);

@@ -217,14 +217,21 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_ring_kernel(const float *__
 
 // The ring kernel takes the problem when it fits its tiling (the caller has checked splits > 1 and the
 // slab): returns HICGAT_EUNSUPPORTED otherwise, and the caller uses gemm_kernel<128, 128, ...>.
+// Whether a K-split weight gradient fits the ring kernel's tiling (whole 128 x 128 tiles up to 1024,
+// rows and operands the 16-byte LDS-DMA copies can read): the one statement of it, asked by the
+// dispatch of gemm.hip (and its hicgat_gemm_form) and by the launch below.  Addresses: alignment only.
+bool gemm_wgrad_ring_fits(const void *A, int64_t lda, const void *B, int64_t ldb, int M, int N, int K, int splits) {
+  const bool al = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
+  if (!al || M % WBM || N % WBN || M < WBM || N < WBN || M > 1024 || N > 1024 || lda % 4 || ldb % 4 || K < 1)
+    return false;
+  return (int64_t)(M / WBM) * (N / WBN) * splits <= 0x7fffffff;
+}
+
 int gemm_wgrad_ring_launch(const float *A, int64_t lda, const float *B, int64_t ldb, int M, int N, int K, int kchunk,
                            int splits, float *slab, int64_t slab_stride, hipStream_t s) {
-  const bool al = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
-  if (!al || M % WBM || N % WBN || M < WBM || N < WBN || M > 1024 || N > 1024 || lda % 4 || ldb % 4 || K < 1 ||
-      kchunk % WBK)
-    return HICGAT_EUNSUPPORTED;
+  // kchunk: the caller's split depth, whole 16-deep stages (launch<> of gemm.hip rounds it so)
+  if (!gemm_wgrad_ring_fits(A, lda, B, ldb, M, N, K, splits) || kchunk % WBK) return HICGAT_EUNSUPPORTED;
   const int64_t wgs = (int64_t)(M / WBM) * (N / WBN) * splits;
-  if (wgs > 0x7fffffff) return HICGAT_EUNSUPPORTED;
   hipLaunchKernelGGL(gemm_wgrad_ring_kernel, dim3((unsigned)wgs), dim3(256), 0, s, A, lda, B, ldb, M, N, K, kchunk,
                      slab, slab_stride);
   HICGAT_CHECK_LAUNCH();

@@ -115,6 +115,7 @@ SIGNATURES = {
                             c_int, c_int, c_p, c_sz, c_p]),
     "hicgat_gemm_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "hicgat_gemm_row_splits": (c_int, [c_int, c_int, c_int]),
+    "hicgat_gemm_form": (c_int, [c_int, c_int, c_int, c_int, c_int, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int]),
     "hicgat_gemm_wgrad": (c_int, [c_int, c_int, c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p,
                                   c_sz, c_p]),
     "hicgat_gemm_wgrad_workspace_bytes": (c_sz, [c_int, c_int, c_int]),

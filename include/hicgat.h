@@ -466,6 +466,33 @@ size_t hicgat_gemm_workspace_bytes(int M, int N, int splits);
  * the dispatch's own tile rule.  A pure function of its arguments: no stream, no HIP call, no GPU
  * needed (as hicgat_pairdist_num_tiles). */
 int hicgat_gemm_row_splits(int M, int N, int K);
+/* The form a hicgat_gemm or hicgat_gemm_wgrad call with these arguments launches, decided by the very
+ * predicates the dispatch uses (tests assert through it that they reach the kernel they name).  A and
+ * B are read for their alignment only and never dereferenced.  with_db = 0: a hicgat_gemm call.  A
+ * hicgat_gemm_wgrad call is a_kmajor = b_kmajor = 1, impl = HICGAT_GEMM_F32 (it never takes the ring
+ * kernel) and with_db = (db != NULL); with_db != 0 in any other layout is HICGAT_EINVAL.
+ * Returns HICGAT_EINVAL / HICGAT_EUNSUPPORTED where the call would for these arguments (sizes, splits,
+ * impl, NULL operands), HICGAT_GEMM_FORM_NONE (0) where it returns without a launch (M == 0 or N == 0),
+ * else the bits
+ *   HICGAT_GEMM_FORM_KERNEL (mask)  HICGAT_GEMM_FORM_GEMM_KERNEL (gemm.hip's register-staged
+ *                                   gemm_kernel), _TALL (gemm_tall.hip, 160 x 128 LDS-DMA) or _RING
+ *                                   (gemm_wgrad.hip, 128 x 128 LDS-DMA slabs)
+ *   HICGAT_GEMM_FORM_TILE (mask)    HICGAT_GEMM_FORM_64x64, _64x128, _128x128 or _160x128
+ *   HICGAT_GEMM_FORM_VEC            16-byte staging (float4 loads; always set for the LDS-DMA kernels),
+ *                                   clear: scalar staging (a dimension or leading dimension that is no
+ *                                   multiple of 4, or an operand that is not 16-byte aligned)
+ *   HICGAT_GEMM_FORM_DB             gemm_kernel with double-buffered LDS
+ *   HICGAT_GEMM_FORM_CS             gemm_kernel with the bias-gradient column sums
+ * Pure host arithmetic: no stream, no HIP call, no GPU needed. */
+enum {
+  HICGAT_GEMM_FORM_NONE = 0,
+  HICGAT_GEMM_FORM_GEMM_KERNEL = 1, HICGAT_GEMM_FORM_TALL = 2, HICGAT_GEMM_FORM_RING = 3, HICGAT_GEMM_FORM_KERNEL = 3,
+  HICGAT_GEMM_FORM_64x64 = 0 << 2, HICGAT_GEMM_FORM_64x128 = 1 << 2, HICGAT_GEMM_FORM_128x128 = 2 << 2,
+  HICGAT_GEMM_FORM_160x128 = 3 << 2, HICGAT_GEMM_FORM_TILE = 3 << 2,
+  HICGAT_GEMM_FORM_VEC = 1 << 4, HICGAT_GEMM_FORM_DB = 1 << 5, HICGAT_GEMM_FORM_CS = 1 << 6
+};
+int hicgat_gemm_form(int a_kmajor, int b_kmajor, int M, int N, int K, const void *A, int64_t lda, const void *B,
+                     int64_t ldb, int splits, int impl, int with_db);
 /* Weight AND bias gradient of a Linear in one GEMM (replaces the dW GEMM + bias column sum of the
  * Linear backward, torch.nn.Linear via ATen addmm_backward / sum(0), models.py:637-659):
  *   dW[M,N] (+)= dY^T X  (dY [K,M] and X [K,N] row-major, K = node rows),

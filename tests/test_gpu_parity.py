@@ -293,22 +293,38 @@ def test_gemm_layouts_match_torch(m, n, k):
 
 @pytest.mark.parametrize("m,n,k", [(20001, 512, 512), (1601, 128, 48), (2000, 384, 16)])
 def test_tall_gemm_edges_and_accumulate(m, n, k):
-    """The 160x128 LDS-DMA kernel (gemm_tall.hip) on ragged row counts, both B layouts, bias and
-    accumulate, against fp64."""
+    """Node-row GEMMs on ragged row counts, both B layouts, bias and accumulate, against fp64.  Which
+    kernel each call runs (asserted through hicgat_gemm_form): at (20001, 512, 512), 504 tiles, the
+    160x128 LDS-DMA kernel (gemm_tall.hip) in both layouts; (1601, 128, 48) and (2000, 384, 16) are 11
+    and 39 tiles, below the 192 from which the tall kernel is taken, and run gemm_kernel's 64x128 tile
+    (forward) and its double-buffered 64x64 tile (input gradient: 48 and 16 output columns).  The
+    row-strided operand starts 8 bytes into its row, which no 16-byte copy can read: every shape runs it
+    on the scalar-staged 64x128 tile.  (tests/test_gpu_gemm_edges.py holds the tall kernel's own edges.)"""
+    import gemm_ref
     import hicgat
+    from hicgat import _lib
     K = hicgat.kernels.default()
+
+    def form(b_km, M, N, Kd, A, B):   # with the K split that K.gemm picks for the call (kernels.row_splits)
+        return gemm_ref.form_name(_lib.load().hicgat_gemm_form(0, b_km, M, N, Kd, A.data_ptr(), A.stride(0), B.data_ptr(),
+                                                               B.stride(0), hicgat.kernels.row_splits(M, N, Kd), 0, 0))
+
+    tall = m == 20001
     torch.manual_seed(m + n + k)
     x = torch.randn(m, k, device=DEV)
     w = torch.randn(n, k, device=DEV)
     b = torch.randn(n, device=DEV)
     y0 = torch.randn(m, n, device=DEV)
+    assert form(0, m, n, k, x, w) == ("tall 160x128 vec" if tall else "gemm_kernel 64x128 vec")
     y = K.gemm(0, 0, m, n, k, x, w, y0.clone(), bias=b, accumulate=True)
     assert _rel(y.cpu(), (x.double() @ w.double().t() + b.double() + y0.double()).cpu()) < 5e-6
     dy = torch.randn(m, n, device=DEV)
+    assert form(1, m, k, n, dy, w) == ("tall 160x128 vec" if tall else "gemm_kernel 64x64 vec db")
     dx = K.gemm(0, 1, m, k, n, dy, w, torch.empty(m, k, device=DEV))
     assert _rel(dx.cpu(), (dy.double() @ w.double()).cpu()) < 5e-6
-    if n % 128 == 0 and k % 16 == 0:   # same numbers with the tall kernel's strided-row operands
+    if n % 128 == 0 and k % 16 == 0:   # same numbers with row-strided operands
         xs = torch.randn(m, k + 4, device=DEV)[:, 2:2 + k]
+        assert form(0, m, n, k, xs, w) == "gemm_kernel 64x128 scalar"
         ys = K.gemm(0, 0, m, n, k, xs, w, torch.empty(m, n, device=DEV), bias=b)
         assert _rel(ys.cpu(), (xs.double() @ w.double().t() + b.double()).cpu()) < 5e-6
 

@@ -154,15 +154,19 @@ def test_xagg_gemm_calls_match_float64(shape):
     assert err < 1e-5
 
 
+@pytest.mark.parametrize("small_m", [16, 0])
 @pytest.mark.parametrize("target", [64, 512])
-def test_param_grads_grouped_matches_float64(target):
+def test_param_grads_grouped_matches_float64(target, small_m):
     """hicgat_param_grads_grouped (the sharded step's one-launch parameter gradients) against
     float64 torch: weight-gradient jobs of the step's shapes -- a 512 x 512 dual-Linear pair with
     its bias, the two per-head 256 x 512 blocks of lin_l (row views of one [512, 512] gradient) with
-    their bias halves, dense3's 3 x 64 (scalar-staged tile), g_dst's 2 x 512 from a strided [R, 8]
-    row-stats view (overwrite) -- and column-sum jobs (LayerNorm partial rows into an adjacent
-    [dgamma | dbeta], a [blocks, 1024] partial-row sum that overwrites); ``target`` = the workgroup
-    budget (64: few K chunks, 512: many).  Then the same call again must give the same bits."""
+    their bias halves, dense3's 3 x 64, g_dst's 2 x 512 from a strided [R, 8] row-stats view
+    (overwrite) -- and column-sum jobs (LayerNorm partial rows into an adjacent [dgamma | dbeta], a
+    [blocks, 1024] partial-row sum that overwrites); ``target`` = the workgroup budget (64: few K
+    chunks, 512: many).  ``small_m`` = 16 (kernels.SMALL_M, the default): the 3 x 64 and 2 x 512 jobs
+    become weighted column sums and never reach wgrad_grouped_kernel; 0 (paramgrads.SIDE_SMALL_M, what
+    the flagship step runs): they are scalar-staged 128 x 128 tiles of it, with the bias-gradient column
+    sums.  Then the same call again must give the same bits."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import hicgat
@@ -198,7 +202,7 @@ def test_param_grads_grouped_matches_float64(target):
         w = [(dY, x, Wg, bg, True), (dc, z3, W3g, b3g, True), (rs[:, 6:8], x, gdst, None, False)]
         w += [(dout[:, hd * 256:(hd + 1) * 256], x, Wl[hd * 256:(hd + 1) * 256], bl[hd * 256:(hd + 1) * 256], True)
               for hd in range(2)]
-        K.param_grads_grouped(w, [(lnp, lng, True), (gp, gs, False)], target_wgs=target)
+        K.param_grads_grouped(w, [(lnp, lng, True), (gp, gs, False)], target_wgs=target, small_m=small_m)
         torch.cuda.synchronize()
         res.append({k: v.clone() for k, v in outs.items()})
     errs = {k: _rel(res[0][k], ref[k]) for k in ref}
