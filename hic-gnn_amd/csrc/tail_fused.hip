@@ -24,7 +24,10 @@
 #include "pack.hpp"
 
 #include <algorithm>
+#include <cstddef>
+#include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 namespace hicgat {
@@ -777,19 +780,25 @@ extern "C" int hicgat_step_begin_pack(float *grad, int64_t n, int64_t *step_coun
 }
 
 namespace {
-struct TailHeads {   // the HEADS operands of the head-fused forms (all null: the plain tail)
-  const float *xa = nullptr;
-  int64_t xa_hs = 0;
-  const float *Wh = nullptr, *bh = nullptr;
-  float *Y0 = nullptr, *O = nullptr;
-};
+// The operand structs of include/hicgat.h lead with the pointers a direction requires: whether any of
+// the first N pointer members of s is NULL.
+template <int N, class T>
+bool any_null(const T &s) {
+  static_assert(std::is_standard_layout<T>::value && sizeof(T) >= N * sizeof(void *), "N leading pointers");
+  const void *p[N];
+  std::memcpy(p, &s, sizeof(p));
+  return std::find(p, p + N, nullptr) != p + N;
+}
+static_assert(offsetof(hicgat_tail_weights, b1c) == 10 * sizeof(void *) &&
+                  offsetof(hicgat_tail_weights, eps) == 14 * sizeof(void *) &&
+                  offsetof(hicgat_tail_acts, z1) == 6 * sizeof(void *) &&
+                  sizeof(hicgat_tail_acts) == 9 * sizeof(void *) &&
+                  offsetof(hicgat_tail_grads, dx) == 6 * sizeof(void *),
+              "any_null's counts below");
 
 template <bool HEADS, bool PK>
-int tail_fwd_go(const float *x, int64_t ldx, int M, const float *W1c, const float *b1c, const float *g1,
-                const float *be1, const float *W2c, const float *b2c, const float *g2, const float *be2, const float *W3,
-                const float *b3, const float *g3, const float *be3, const float *W4, const float *b4, float eps,
-                float *Y1, float *st1, float *z1, float *Y2, float *st2, float *z2, float *y3, float *st3, float *z3,
-                float *coords, const float *Wh, const TailHeads &hh, hipStream_t stream) {
+int tail_fwd_go(const hicgat_tail_weights &w, const float *x, int64_t ldx, int M, const hicgat_tail_acts &a,
+                float *coords, const hicgat_tail_gat &g, hipStream_t stream) {
   // 16 rows per workgroup (66 KiB of dynamic LDS: two workgroups per CU).  A 32-row form (132 KiB,
   // one per CU, each weight fetch serving twice the rows) measured slower at N = 20000 (the one-kernel
   // tail 1.977 vs 1.913 ms per step for the per-layer kernels, profiles/r03r_ab_fused_tail.txt):
@@ -809,10 +818,11 @@ int tail_fwd_go(const float *x, int64_t ldx, int M, const float *W1c, const floa
           hipSuccess;
       if (!pattr) return HICGAT_ELAUNCH;
       hipLaunchKernelGGL((tail_fwd_kernel<RB, NW, false, PK, true>), dim3(ncu), dim3(64 * NW),
-                         (size_t)3 * RB * XS * sizeof(float), stream, x, ldx, M, W1c, b1c, g1, be1, W2c, b2c, g2, be2,
-                         W3, b3, g3, be3, W4, b4, eps, Y1, reinterpret_cast<float2 *>(st1), z1, Y2,
-                         reinterpret_cast<float2 *>(st2), z2, y3, reinterpret_cast<float2 *>(st3), z3, coords,
-                         (int64_t)0, nullptr, nullptr, nullptr, nullptr, ntiles);
+                         (size_t)3 * RB * XS * sizeof(float), stream, x, ldx, M, w.W1c, w.b1c, w.g1, w.be1, w.W2c,
+                         w.b2c, w.g2, w.be2, w.W3, w.b3, w.g3, w.be3, w.W4, w.b4, w.eps, a.Y1,
+                         reinterpret_cast<float2 *>(a.st1), a.z1, a.Y2, reinterpret_cast<float2 *>(a.st2), a.z2, a.y3,
+                         reinterpret_cast<float2 *>(a.st3), a.z3, coords, (int64_t)0, nullptr, nullptr, nullptr,
+                         nullptr, ntiles);
       HICGAT_CHECK_LAUNCH();
       return HICGAT_OK;
     }
@@ -822,72 +832,46 @@ int tail_fwd_go(const float *x, int64_t ldx, int M, const float *W1c, const floa
                                                2 * RB * XS * (int)sizeof(float)) == hipSuccess;
   if (!attr) return HICGAT_ELAUNCH;
   hipLaunchKernelGGL((tail_fwd_kernel<RB, NW, HEADS, PK>), dim3(ntiles), dim3(64 * NW),
-                     (size_t)2 * RB * XS * sizeof(float), stream, x, ldx, M, W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3,
-                     b3, g3, be3, W4, b4, eps, Y1, reinterpret_cast<float2 *>(st1), z1, Y2,
-                     reinterpret_cast<float2 *>(st2), z2, y3, reinterpret_cast<float2 *>(st3), z3, coords, hh.xa_hs,
-                     Wh, hh.bh, hh.Y0, hh.O);
+                     (size_t)2 * RB * XS * sizeof(float), stream, x, ldx, M, w.W1c, w.b1c, w.g1, w.be1, w.W2c, w.b2c,
+                     w.g2, w.be2, w.W3, w.b3, w.g3, w.be3, w.W4, w.b4, w.eps, a.Y1, reinterpret_cast<float2 *>(a.st1),
+                     a.z1, a.Y2, reinterpret_cast<float2 *>(a.st2), a.z2, a.y3, reinterpret_cast<float2 *>(a.st3),
+                     a.z3, coords, g.xa_head_stride, g.Wh, g.bh, g.Y0, g.O);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
 }
 
+// w and g by value: the packed form substitutes its copies of W1c / W2c / Wh
 template <bool HEADS>
-int tail_fwd_launch(const float *x, int64_t ldx, int M, const float *W1c, const float *b1c, const float *g1,
-                    const float *be1, const float *W2c, const float *b2c, const float *g2, const float *be2,
-                    const float *W3, const float *b3, const float *g3, const float *be3, const float *W4,
-                    const float *b4, float eps, float *Y1, float *st1, float *z1, float *Y2, float *st2, float *z2,
-                    float *y3, float *st3, float *z3, float *coords, const TailHeads &hh, const void *pack,
-                    hipStream_t stream) {
+int tail_fwd_launch(const hicgat_tail_weights *wp, const float *x, int64_t ldx, int M, const hicgat_tail_acts *a,
+                    float *coords, hicgat_tail_gat g, hipStream_t stream) {
   if (M < 0 || ldx < 512 || (ldx & 3)) return HICGAT_EINVAL;
   if (M == 0) return HICGAT_OK;
-  const void *ps[] = {x, W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4,
-                      Y1, st1, z1, Y2, st2, z2, y3, st3, z3, coords};
-  for (const void *p : ps)
-    if (!p) return HICGAT_EINVAL;
-  if (HEADS && (!hh.Wh || !hh.bh || !hh.Y0 || !hh.O || (hh.xa_hs & 3))) return HICGAT_EINVAL;
+  if (!wp || !a || !x || !coords || any_null<14>(*wp) || any_null<9>(*a)) return HICGAT_EINVAL;
+  if (HEADS && (!g.Wh || !g.bh || !g.Y0 || !g.O || (g.xa_head_stride & 3))) return HICGAT_EINVAL;
+  hicgat_tail_weights w = *wp;
   // float4 rows: x, the weight rows and the LDS images need 16-B alignment
-  if (((uintptr_t)x | (uintptr_t)W1c | (uintptr_t)W2c | (uintptr_t)W3 | (uintptr_t)hh.Wh | (uintptr_t)hh.Y0 |
-       (uintptr_t)hh.O | (uintptr_t)pack) & 15)
+  if (((uintptr_t)x | (uintptr_t)w.W1c | (uintptr_t)w.W2c | (uintptr_t)w.W3 | (uintptr_t)g.Wh | (uintptr_t)g.Y0 |
+       (uintptr_t)g.O | (uintptr_t)w.pack) & 15)
     return HICGAT_EUNSUPPORTED;
-  if (pack) {
-    if (HEADS && !pack_has_heads(pack)) return HICGAT_EINVAL;   // packed without Wh
-    const float *pk = static_cast<const float *>(pack);
-    return tail_fwd_go<HEADS, true>(x, ldx, M, pk + kPackF1, b1c, g1, be1, pk + kPackF2, b2c, g2, be2, W3, b3, g3,
-                                    be3, W4, b4, eps, Y1, st1, z1, Y2, st2, z2, y3, st3, z3, coords,
-                                    HEADS ? pk + kPackFH : nullptr, hh, stream);
-  }
-  return tail_fwd_go<HEADS, false>(x, ldx, M, W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4, eps, Y1,
-                                   st1, z1, Y2, st2, z2, y3, st3, z3, coords, hh.Wh, hh, stream);
+  if (!w.pack) return tail_fwd_go<HEADS, false>(w, x, ldx, M, *a, coords, g, stream);
+  if (HEADS && !pack_has_heads(w.pack)) return HICGAT_EINVAL;   // packed without Wh
+  const float *pk = static_cast<const float *>(w.pack);
+  w.W1c = pk + kPackF1;
+  w.W2c = pk + kPackF2;
+  g.Wh = HEADS ? pk + kPackFH : nullptr;
+  return tail_fwd_go<HEADS, true>(w, x, ldx, M, *a, coords, g, stream);
 }
 }  // namespace
 
-extern "C" int hicgat_tail_fwd_fused(const float *x, int64_t ldx, int M, const float *W1c, const float *b1c,
-                                     const float *g1, const float *be1, const float *W2c, const float *b2c,
-                                     const float *g2, const float *be2, const float *W3, const float *b3,
-                                     const float *g3, const float *be3, const float *W4, const float *b4, float eps,
-                                     float *Y1, float *st1, float *z1, float *Y2, float *st2, float *z2, float *y3,
-                                     float *st3, float *z3, float *coords, const void *pack, hicgat_stream_t stream) {
-  return tail_fwd_launch<false>(x, ldx, M, W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4, eps, Y1,
-                                st1, z1, Y2, st2, z2, y3, st3, z3, coords, TailHeads{}, pack, (hipStream_t)stream);
-}
-
-extern "C" int hicgat_tail_fwd_fused_heads(const float *xa, int64_t ld_xa, int64_t xa_head_stride, const float *Wh,
-                                           const float *bh, float *Y0, float *O, int M, const float *W1c,
-                                           const float *b1c, const float *g1, const float *be1, const float *W2c,
-                                           const float *b2c, const float *g2, const float *be2, const float *W3,
-                                           const float *b3, const float *g3, const float *be3, const float *W4,
-                                           const float *b4, float eps, float *Y1, float *st1, float *z1, float *Y2,
-                                           float *st2, float *z2, float *y3, float *st3, float *z3, float *coords,
-                                           const void *pack, hicgat_stream_t stream) {
+extern "C" int hicgat_tail_fwd(const hicgat_tail_weights *weights, const float *x, int64_t ldx, int M,
+                               const hicgat_tail_acts *acts, float *coords, const hicgat_tail_gat *gat,
+                               hicgat_stream_t stream) {
+  const int form = gat ? gat->form : HICGAT_TAIL_PLAIN;
+  if (form == HICGAT_TAIL_PLAIN)   // no field of gat is read
+    return tail_fwd_launch<false>(weights, x, ldx, M, acts, coords, hicgat_tail_gat{}, (hipStream_t)stream);
+  if (form != HICGAT_TAIL_HEADS) return HICGAT_EINVAL;   // ROWS is a form of the backward
   if (kTailWaves < 8) return HICGAT_EUNSUPPORTED;
-  TailHeads hh;
-  hh.xa = xa;
-  hh.xa_hs = xa_head_stride;
-  hh.Wh = Wh;
-  hh.bh = bh;
-  hh.Y0 = Y0;
-  hh.O = O;
-  return tail_fwd_launch<true>(xa, ld_xa, M, W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4, eps, Y1,
-                               st1, z1, Y2, st2, z2, y3, st3, z3, coords, hh, pack, (hipStream_t)stream);
+  return tail_fwd_launch<true>(weights, x, ldx, M, acts, coords, *gat, (hipStream_t)stream);
 }
 
 extern "C" int hicgat_tail_bwd_waves(void) { return kTailWaves; }
@@ -900,18 +884,9 @@ extern "C" size_t hicgat_tail_bwd_workspace_bytes(int M, int W) {
 }
 
 namespace {
-struct TailHeadsBwd {   // the HEADS / ROWS operands of the backward (all null: the plain tail)
-  int act = 0;
-  const float *Y0 = nullptr, *Wh = nullptr, *bh = nullptr, *out2 = nullptr;
-  float *dout = nullptr, *row_stats = nullptr, *dxa = nullptr;
-};
-
-template <bool HEADS, bool PK, bool ROWS = false>
-int tail_bwd_go(const float *dcoords, int M, const float *Y1, const float *st1, const float *Y2, const float *st2,
-                const float *y3, const float *st3, const float *W4, const float *W3, const float *W2c, const float *W1c,
-                const float *g1, const float *be1, const float *g2, const float *be2, const float *g3,
-                const float *be3, float *dx, float *dY1, float *dY2, float *dy3, void *ws1, void *ws2, void *ws3,
-                const float *Wh, const TailHeadsBwd &hh, hipStream_t stream) {
+template <bool HEADS, bool PK, bool ROWS>
+int tail_bwd_go(const hicgat_tail_weights &w, const hicgat_tail_acts &a, const float *dcoords, int M,
+                const hicgat_tail_grads &d, const hicgat_tail_gat &g, hipStream_t stream) {
   constexpr int RB = kTailBwdRows, NW = kTailWaves;
   // [As | Bs] row images + the [NW][2 x 256] LayerNorm partial scratch
   constexpr int kBwdLds = (2 * RB * XS + NW * 2 * 256) * (int)sizeof(float);
@@ -920,103 +895,58 @@ int tail_bwd_go(const float *dcoords, int M, const float *Y1, const float *st1, 
                                                kBwdLds) == hipSuccess;
   if (!attr) return HICGAT_ELAUNCH;
   hipLaunchKernelGGL((tail_bwd_kernel<RB, NW, HEADS, PK, ROWS>), dim3((M + RB - 1) / RB), dim3(64 * NW),
-                     (size_t)kBwdLds, stream, dcoords, M, Y1, reinterpret_cast<const float2 *>(st1),
-                     Y2, reinterpret_cast<const float2 *>(st2), y3, reinterpret_cast<const float2 *>(st3), W4, W3, W2c,
-                     W1c, g1, be1, g2, be2, g3, be3, dx, dY1, dY2, dy3, static_cast<float *>(ws1),
-                     static_cast<float *>(ws2), static_cast<float *>(ws3), hh.act, hh.Y0, Wh, hh.bh, hh.dout,
-                     hh.row_stats, hh.dxa, hh.out2);
+                     (size_t)kBwdLds, stream, dcoords, M, a.Y1, reinterpret_cast<const float2 *>(a.st1), a.Y2,
+                     reinterpret_cast<const float2 *>(a.st2), a.y3, reinterpret_cast<const float2 *>(a.st3), w.W4,
+                     w.W3, w.W2c, w.W1c, w.g1, w.be1, w.g2, w.be2, w.g3, w.be3, (HEADS || ROWS) ? nullptr : d.dx,
+                     d.dY1, d.dY2, d.dy3, static_cast<float *>(d.ws[0]), static_cast<float *>(d.ws[1]),
+                     static_cast<float *>(d.ws[2]), g.act ? 1 : 0, g.Y0, g.Wh, g.bh, g.dout, g.row_stats, g.dxa,
+                     g.out2);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
 }
 
-template <bool HEADS, bool ROWS = false>
-int tail_bwd_launch(const float *dcoords, int M, const float *Y1, const float *st1, const float *Y2, const float *st2,
-                    const float *y3, const float *st3, const float *W4, const float *W3, const float *W2c,
-                    const float *W1c, const float *g1, const float *be1, const float *g2, const float *be2,
-                    const float *g3, const float *be3, float *dx, float *dY1, float *dY2, float *dy3, void *ws1,
-                    size_t ws1_bytes, void *ws2, size_t ws2_bytes, void *ws3, size_t ws3_bytes,
-                    const TailHeadsBwd &hh, const void *pack, hipStream_t stream) {
+// g by value, and w copied: the packed form substitutes its copies of W1c / W2c / Wh
+template <bool HEADS, bool ROWS>
+int tail_bwd_launch(const hicgat_tail_weights *wp, const hicgat_tail_acts *a, const float *dcoords, int M,
+                    const hicgat_tail_grads *d, hicgat_tail_gat g, hipStream_t stream) {
   if (M < 0) return HICGAT_EINVAL;
   if (M == 0) return HICGAT_OK;
-  const void *ps[] = {dcoords, Y1, st1, Y2, st2, y3, st3, W4, W3, W2c, W1c, g1, be1, g2, be2, g3, be3,
-                      (HEADS || ROWS) ? hh.dout : dx, dY1, dY2, dy3, ws1, ws2, ws3};
-  for (const void *p : ps)
-    if (!p) return HICGAT_EINVAL;
-  if (HEADS && (!hh.Y0 || !hh.Wh || !hh.bh || !hh.row_stats || !hh.dxa)) return HICGAT_EINVAL;
-  if (ROWS && (!hh.Y0 || !hh.bh || !hh.out2 || !hh.row_stats)) return HICGAT_EINVAL;
-  if ((HEADS || ROWS) &&
-      (((uintptr_t)hh.Y0 | (uintptr_t)hh.bh | (uintptr_t)hh.dout | (uintptr_t)hh.row_stats | (uintptr_t)hh.out2) & 15))
-    return HICGAT_EUNSUPPORTED;
-  if ((uintptr_t)pack & 15) return HICGAT_EUNSUPPORTED;
-  // every workgroup owns NW partial rows of each LN workspace (one per wave)
-  if (ws1_bytes < hicgat_tail_bwd_workspace_bytes(M, 256) || ws2_bytes < hicgat_tail_bwd_workspace_bytes(M, 128) ||
-      ws3_bytes < hicgat_tail_bwd_workspace_bytes(M, 64))
+  if (!wp || !a || !d || !dcoords || any_null<10>(*wp) || any_null<6>(*a) || any_null<6>(*d) ||
+      !((HEADS || ROWS) ? g.dout : d->dx))
     return HICGAT_EINVAL;
-  if (pack) {
-    if (HEADS && !pack_has_heads(pack)) return HICGAT_EINVAL;   // packed without Wh
-    const float *pk = static_cast<const float *>(pack);
-    return tail_bwd_go<HEADS, true, ROWS>(dcoords, M, Y1, st1, Y2, st2, y3, st3, W4, W3, pk + kPackB2, pk + kPackB1,
-                                          g1, be1, g2, be2, g3, be3, dx, dY1, dY2, dy3, ws1, ws2, ws3,
-                                          HEADS ? pk + kPackBH : nullptr, hh, stream);
-  }
-  return tail_bwd_go<HEADS, false, ROWS>(dcoords, M, Y1, st1, Y2, st2, y3, st3, W4, W3, W2c, W1c, g1, be1, g2, be2, g3,
-                                         be3, dx, dY1, dY2, dy3, ws1, ws2, ws3, hh.Wh, hh, stream);
+  if (HEADS && (!g.Y0 || !g.Wh || !g.bh || !g.row_stats || !g.dxa)) return HICGAT_EINVAL;
+  if (ROWS && (!g.Y0 || !g.bh || !g.out2 || !g.row_stats)) return HICGAT_EINVAL;
+  hicgat_tail_weights w = *wp;
+  if ((HEADS || ROWS) &&
+      (((uintptr_t)g.Y0 | (uintptr_t)g.bh | (uintptr_t)g.dout | (uintptr_t)g.row_stats | (uintptr_t)g.out2) & 15))
+    return HICGAT_EUNSUPPORTED;
+  if ((uintptr_t)w.pack & 15) return HICGAT_EUNSUPPORTED;
+  // every workgroup owns one partial row of each LN workspace
+  for (int i = 0; i < 3; ++i)
+    if (d->ws_bytes[i] < hicgat_tail_bwd_workspace_bytes(M, 256 >> i)) return HICGAT_EINVAL;
+  if (!w.pack) return tail_bwd_go<HEADS, false, ROWS>(w, *a, dcoords, M, *d, g, stream);
+  if (HEADS && !pack_has_heads(w.pack)) return HICGAT_EINVAL;   // packed without Wh
+  const float *pk = static_cast<const float *>(w.pack);
+  w.W1c = pk + kPackB1;
+  w.W2c = pk + kPackB2;
+  g.Wh = HEADS ? pk + kPackBH : nullptr;
+  return tail_bwd_go<HEADS, true, ROWS>(w, *a, dcoords, M, *d, g, stream);
 }
 }  // namespace
 
-extern "C" int hicgat_tail_bwd_fused(const float *dcoords, int M, const float *Y1, const float *st1, const float *Y2,
-                                     const float *st2, const float *y3, const float *st3, const float *W4,
-                                     const float *W3, const float *W2c, const float *W1c, const float *g1,
-                                     const float *be1, const float *g2, const float *be2, const float *g3,
-                                     const float *be3, float *dx, float *dY1, float *dY2, float *dy3, void *ws1,
-                                     size_t ws1_bytes, void *ws2, size_t ws2_bytes, void *ws3, size_t ws3_bytes,
-                                     const void *pack, hicgat_stream_t stream) {
-  return tail_bwd_launch<false>(dcoords, M, Y1, st1, Y2, st2, y3, st3, W4, W3, W2c, W1c, g1, be1, g2, be2, g3, be3,
-                                dx, dY1, dY2, dy3, ws1, ws1_bytes, ws2, ws2_bytes, ws3, ws3_bytes, TailHeadsBwd{}, pack,
-                                (hipStream_t)stream);
-}
-
-extern "C" int hicgat_tail_bwd_fused_rows(const float *dcoords, int M, const float *Y1, const float *st1,
-                                          const float *Y2, const float *st2, const float *y3, const float *st3,
-                                          const float *W4, const float *W3, const float *W2c, const float *W1c,
-                                          const float *g1, const float *be1, const float *g2, const float *be2,
-                                          const float *g3, const float *be3, float *dY1, float *dY2, float *dy3,
-                                          void *ws1, size_t ws1_bytes, void *ws2, size_t ws2_bytes, void *ws3,
-                                          size_t ws3_bytes, int act, const float *y, const float *out2,
-                                          const float *bias, float *dout, float *row_stats, const void *pack,
-                                          hicgat_stream_t stream) {
-  if (kTailWaves != 16) return HICGAT_EUNSUPPORTED;   // one row per wave
-  TailHeadsBwd hh;
-  hh.act = act ? 1 : 0;
-  hh.Y0 = y;
-  hh.bh = bias;
-  hh.out2 = out2;
-  hh.dout = dout;
-  hh.row_stats = row_stats;
-  return tail_bwd_launch<false, true>(dcoords, M, Y1, st1, Y2, st2, y3, st3, W4, W3, W2c, W1c, g1, be1, g2, be2, g3,
-                                      be3, nullptr, dY1, dY2, dy3, ws1, ws1_bytes, ws2, ws2_bytes, ws3, ws3_bytes, hh,
-                                      pack, (hipStream_t)stream);
-}
-
-extern "C" int hicgat_tail_bwd_fused_heads(const float *dcoords, int M, const float *Y1, const float *st1,
-                                           const float *Y2, const float *st2, const float *y3, const float *st3,
-                                           const float *W4, const float *W3, const float *W2c, const float *W1c,
-                                           const float *g1, const float *be1, const float *g2, const float *be2,
-                                           const float *g3, const float *be3, float *dY1, float *dY2, float *dy3,
-                                           void *ws1, size_t ws1_bytes, void *ws2, size_t ws2_bytes, void *ws3,
-                                           size_t ws3_bytes, int act, const float *Y0, const float *Wh,
-                                           const float *bh, float *dout, float *row_stats, float *dxa,
-                                           const void *pack, hicgat_stream_t stream) {
-  if (kTailWaves < 8) return HICGAT_EUNSUPPORTED;
-  TailHeadsBwd hh;
-  hh.act = act ? 1 : 0;
-  hh.Y0 = Y0;
-  hh.Wh = Wh;
-  hh.bh = bh;
-  hh.dout = dout;
-  hh.row_stats = row_stats;
-  hh.dxa = dxa;
-  return tail_bwd_launch<true>(dcoords, M, Y1, st1, Y2, st2, y3, st3, W4, W3, W2c, W1c, g1, be1, g2, be2, g3, be3,
-                               nullptr, dY1, dY2, dy3, ws1, ws1_bytes, ws2, ws2_bytes, ws3, ws3_bytes, hh, pack,
-                               (hipStream_t)stream);
+extern "C" int hicgat_tail_bwd(const hicgat_tail_weights *weights, const hicgat_tail_acts *acts, const float *dcoords,
+                               int M, const hicgat_tail_grads *grads, const hicgat_tail_gat *gat,
+                               hicgat_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  switch (gat ? gat->form : HICGAT_TAIL_PLAIN) {
+    case HICGAT_TAIL_PLAIN:   // no field of gat is read
+      return tail_bwd_launch<false, false>(weights, acts, dcoords, M, grads, hicgat_tail_gat{}, s);
+    case HICGAT_TAIL_HEADS:
+      if (kTailWaves < 8) return HICGAT_EUNSUPPORTED;
+      return tail_bwd_launch<true, false>(weights, acts, dcoords, M, grads, *gat, s);
+    case HICGAT_TAIL_ROWS:
+      if (kTailWaves != 16) return HICGAT_EUNSUPPORTED;   // one row per wave
+      return tail_bwd_launch<false, true>(weights, acts, dcoords, M, grads, *gat, s);
+  }
+  return HICGAT_EINVAL;
 }

@@ -37,7 +37,36 @@ class GemmJob(ctypes.Structure):
                 ("ldr", c_i64), ("bias", c_p), ("M", c_int), ("N", c_int), ("K", c_int)]
 
 
+def _pointers(names):
+    return [(n, c_p) for n in names.split()]
+
+
+class TailWeights(ctypes.Structure):
+    """include/hicgat.h hicgat_tail_weights."""
+    _fields_ = _pointers("W1c W2c W3 W4 g1 be1 g2 be2 g3 be3 b1c b2c b3 b4") + [("eps", c_f), ("pack", c_p)]
+
+
+class TailActs(ctypes.Structure):
+    """include/hicgat.h hicgat_tail_acts."""
+    _fields_ = _pointers("Y1 st1 Y2 st2 y3 st3 z1 z2 z3")
+
+
+class TailGrads(ctypes.Structure):
+    """include/hicgat.h hicgat_tail_grads."""
+    _fields_ = _pointers("dY1 dY2 dy3") + [("ws", c_p * 3), ("dx", c_p), ("ws_bytes", c_sz * 3)]
+
+
+class TailGat(ctypes.Structure):
+    """include/hicgat.h hicgat_tail_gat; ``form`` is one of TAIL_PLAIN / TAIL_HEADS / TAIL_ROWS."""
+    _fields_ = [("form", c_int), ("act", c_int), ("xa_head_stride", c_i64)] + _pointers(
+        "Wh bh Y0 O out2 dout row_stats dxa")
+
+
+TAIL_PLAIN, TAIL_HEADS, TAIL_ROWS = 0, 1, 2      # include/hicgat.h HICGAT_TAIL_*
+
 c_wjobs, c_cjobs, c_gjobs = ctypes.POINTER(WgradJob), ctypes.POINTER(ColsumJob), ctypes.POINTER(GemmJob)
+c_tailw, c_taila, c_tailg, c_tailgat = (ctypes.POINTER(TailWeights), ctypes.POINTER(TailActs),
+                                        ctypes.POINTER(TailGrads), ctypes.POINTER(TailGat))
 
 # name -> (restype, argtypes); mirrors include/hicgat.h one to one
 SIGNATURES = {
@@ -137,17 +166,11 @@ SIGNATURES = {
     "hicgat_act_bwd": (c_int, [c_p, c_p, c_int, c_int, c_int, c_f, c_p, c_p]),
     "hicgat_tail_pack_bytes": (c_sz, []),
     "hicgat_tail_pack": (c_int, [c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "hicgat_tail_fwd_fused": (c_int, [c_p, c_i64, c_int] + [c_p] * 14 + [c_f] + [c_p] * 10 + [c_p, c_p]),
+    "hicgat_tail_fwd": (c_int, [c_tailw, c_p, c_i64, c_int, c_taila, c_p, c_tailgat, c_p]),
     "hicgat_tail_bwd_waves": (c_int, []),
     "hicgat_tail_bwd_partial_rows": (c_int, [c_int]),
     "hicgat_tail_bwd_workspace_bytes": (c_sz, [c_int, c_int]),
-    "hicgat_tail_bwd_fused": (c_int, [c_p, c_int] + [c_p] * 16 + [c_p] * 4 + [c_p, c_sz] * 3 + [c_p, c_p]),
-    "hicgat_tail_fwd_fused_heads": (c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_int] + [c_p] * 14 + [c_f]
-                                    + [c_p] * 10 + [c_p, c_p]),
-    "hicgat_tail_bwd_fused_rows": (c_int, [c_p, c_int] + [c_p] * 16 + [c_p] * 3 + [c_p, c_sz] * 3
-                                   + [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "hicgat_tail_bwd_fused_heads": (c_int, [c_p, c_int] + [c_p] * 16 + [c_p] * 3 + [c_p, c_sz] * 3
-                                    + [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "hicgat_tail_bwd": (c_int, [c_tailw, c_taila, c_p, c_int, c_tailg, c_tailgat, c_p]),
     "hicgat_sage_weights": (c_int, [c_p, c_int, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "hicgat_sage_agg": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_int, c_int, c_p, c_i64,
                                 c_p]),

@@ -5,6 +5,7 @@ stream-ordered on torch's current stream; the ``timed`` names feed bench.py's li
 The distributed trainer (``hicgat.dist``) is written against this interface only, so its
 partitioning / collective logic can be exercised on CPU in tests with a stand-in object.
 """
+import collections
 import os
 
 import torch
@@ -38,6 +39,17 @@ class _timed:
 
 
 P = _lib.ptr
+
+# The one-kernel MLP tail's weights (tail_fused.hip; include/hicgat.h hicgat_tail_weights has their shapes)
+TailWeights = collections.namedtuple("TailWeights", "W1c b1c g1 be1 W2c b2c g2 be2 W3 b3 g3 be3 W4 b4")
+_TAIL_BWD_READS = "W4 W3 W2c W1c g1 be1 g2 be2 g3 be3".split()
+_TAIL_SAVED = "Y1 st1 z1 Y2 st2 z2 y3 st3 z3".split()      # ``tail_fwd_fused``'s saved tuple, in order
+
+
+def _operands(cls, tensors, **scalars):
+    """An operand struct of ``_lib`` with each tensor's device pointer in the field of its name (None: NULL)."""
+    return cls(**{k: None if t is None else t.data_ptr() for k, t in tensors.items()}, **scalars)
+
 
 # K-split of a node-row GEMM that would leave the chip mostly idle (a rank's shard of the multi-GPU
 # step): the library's rule, hicgat_gemm_row_splits (gemm.hip).  HICGAT_ROW_SPLIT=0: off (A/B).
@@ -590,14 +602,13 @@ class HipKernels:
                    "hicgat_tail_pack")
         return pack
 
-    def tail_fwd_fused(self, x, W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4, eps, coords=None,
-                       heads=None, pack=None):
-        """The flagship's MLP tail forward in one launch (tail_fused.hip): returns (coords, saved)
-        with saved = (Y1, st1, z1, Y2, st2, z2, y3, st3, z3); ``coords`` (contiguous [M, 3]): write
-        the output there (e.g. the rank's rows of the sharded step's all-gather buffer).
-        ``heads`` (``ops.TailHeads``): the head-fused form -- the input rows x (written) are
-        relu(xa^h W_h^T + b^h) of the xagg GATConv (hicgat_tail_fwd_fused_heads).  ``pack``: the
-        ``tail_pack`` copies of these W1c / W2c (/ the heads' W), or None (row-major reads)."""
+    def tail_fwd_fused(self, x, weights, eps, coords=None, heads=None, pack=None):
+        """The flagship's MLP tail forward in one launch (hicgat_tail_fwd) on ``weights`` (a
+        ``TailWeights``): returns (coords, saved) with saved = (Y1, st1, z1, Y2, st2, z2, y3, st3, z3);
+        ``coords`` (contiguous [M, 3]): write the output there (e.g. the rank's rows of the sharded
+        step's all-gather buffer).  ``heads`` (``ops.TailHeads``): the head-fused form -- the input
+        rows x (written) are relu(xa^h W_h^T + b^h) of the xagg GATConv.  ``pack``: the ``tail_pack``
+        copies of these W1c / W2c (/ the heads' W), or None (row-major reads)."""
         M = x.shape[0]
         dev = x.device
         f = dict(dtype=torch.float32, device=dev)
@@ -605,66 +616,62 @@ class HipKernels:
         Y2, z2 = torch.empty((M, 256), **f), torch.empty((M, 128), **f)
         y3, z3 = torch.empty((M, 64), **f), torch.empty((M, 64), **f)
         st1, st2, st3 = (torch.empty((M, 2), **f) for _ in range(3))
+        saved = (Y1, st1, z1, Y2, st2, z2, y3, st3, z3)
         if coords is None:
             coords = torch.empty((M, 3), **f)
         assert coords.shape == (M, 3) and coords.is_contiguous()
-        ws = [W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4]
-        assert all(t.is_contiguous() for t in ws) and x.stride(1) == 1
-        tail = [float(eps), P(Y1), P(st1), P(z1), P(Y2), P(st2), P(z2), P(y3), P(st3), P(z3), P(coords), P(pack),
-                _lib.stream(dev)]
+        assert all(t.is_contiguous() for t in weights) and x.stride(1) == 1
+        src, ldx, gat = x, x.stride(0), None
+        if heads is not None:
+            h = heads
+            assert x.is_contiguous() and x.shape == (M, 512) and h.Y0.shape == (M, 512) and h.Y0.is_contiguous()
+            assert h.X4.shape[2] == M and h.X4.is_contiguous() and h.W.is_contiguous() and h.bias.is_contiguous()
+            src, ldx = h.X4, h.X4.stride(2)
+            gat = _operands(_lib.TailGat, dict(Wh=h.W, bh=h.bias, Y0=h.Y0, O=x), form=_lib.TAIL_HEADS,
+                            xa_head_stride=h.X4.stride(0))
+        w = _operands(_lib.TailWeights, dict(weights._asdict(), pack=pack), eps=float(eps))
+        acts = _operands(_lib.TailActs, dict(zip(_TAIL_SAVED, saved)))
         with _timed("tail_fwd_fused"):
-            if heads is None:
-                _lib.check(self.lib.hicgat_tail_fwd_fused(P(x), x.stride(0), M, *[P(t) for t in ws], *tail),
-                           "hicgat_tail_fwd_fused")
-            else:
-                h = heads
-                assert x.is_contiguous() and x.shape == (M, 512) and h.Y0.shape == (M, 512) and h.Y0.is_contiguous()
-                assert h.X4.shape[2] == M and h.X4.is_contiguous() and h.W.is_contiguous() and h.bias.is_contiguous()
-                _lib.check(self.lib.hicgat_tail_fwd_fused_heads(
-                    P(h.X4), h.X4.stride(2), h.X4.stride(0), P(h.W), P(h.bias), P(h.Y0), P(x), M, *[P(t) for t in ws],
-                    *tail), "hicgat_tail_fwd_fused_heads")
-        return coords, (Y1, st1, z1, Y2, st2, z2, y3, st3, z3)
+            _lib.check(self.lib.hicgat_tail_fwd(w, P(src), ldx, M, acts, P(coords), gat, _lib.stream(dev)),
+                       "hicgat_tail_fwd")
+        return coords, saved
 
-    def tail_bwd_fused(self, dcoords, saved, W4, W3, W2c, W1c, g1, be1, g2, be2, g3, be3, heads=None, pack=None,
-                       rows=None):
-        """The tail's input-gradient chain in one launch (tail_fused.hip): returns (dx, dY1, dY2, dy3,
+    def tail_bwd_fused(self, dcoords, saved, weights, heads=None, pack=None, rows=None):
+        """The tail's input-gradient chain in one launch (hicgat_tail_bwd): returns (dx, dY1, dY2, dy3,
         (ws1, ws2, ws3)) -- the LayerNorm dgamma/dbeta partials stay in the workspaces
         (``ops._ln_param_grads`` sums them).  ``heads``: the head-fused form (dx None; the xagg GATConv's
         dout, delta and dxa written into the ``ops.TailHeads`` buffers instead).  ``rows`` = (act, y,
-        out2, bias, row_stats, dout): the single-GPU GATConv's rows pass in the epilogue
-        (hicgat_tail_bwd_fused_rows; dx None, dout and row_stats[:, 4:8] written instead)."""
-        Y1, st1, z1, Y2, st2, z2, y3, st3, z3 = saved
+        out2, bias, row_stats, dout): the single-GPU GATConv's rows pass in the epilogue (dx None, dout
+        and row_stats[:, 4:8] written instead)."""
         M = dcoords.shape[0]
         dev = dcoords.device
         f = dict(dtype=torch.float32, device=dev)
         dY1, dY2, dy3 = (torch.empty((M, w), **f) for w in (512, 256, 64))
         dx = torch.empty((M, 512), **f) if heads is None and rows is None else None
         ws = [_lib.workspace(self.lib.hicgat_tail_bwd_workspace_bytes(M, w), dev) for w in (256, 128, 64)]
-        ts = [W4, W3, W2c, W1c, g1, be1, g2, be2, g3, be3]
-        assert all(t.is_contiguous() for t in ts) and dcoords.is_contiguous()
-        wsa = [P(ws[0]), ws[0].numel(), P(ws[1]), ws[1].numel(), P(ws[2]), ws[2].numel()]
+        reads = {k: getattr(weights, k) for k in _TAIL_BWD_READS}
+        assert all(t.is_contiguous() for t in reads.values()) and dcoords.is_contiguous()
+        gat = None
+        if rows is not None:
+            act, y, out2, bias, rs, dout = rows
+            for t, w in ((y, 512), (out2, 512), (dout, 512), (rs, 8)):
+                assert t.shape == (M, w) and t.is_contiguous()
+            assert bias.is_contiguous() and bias.numel() == 512
+            gat = _operands(_lib.TailGat, dict(Y0=y, out2=out2, bh=bias, dout=dout, row_stats=rs),
+                            form=_lib.TAIL_ROWS, act=int(act))
+        elif heads is not None:
+            h = heads
+            assert h.dout.shape == (M, 512) and h.dout.is_contiguous() and h.dxa.shape == (M, 1024)
+            assert h.dxa.is_contiguous() and h.rs.shape == (M, 8) and h.rs.is_contiguous()
+            gat = _operands(_lib.TailGat, dict(Y0=h.Y0, Wh=h.W, bh=h.bias, dout=h.dout, row_stats=h.rs, dxa=h.dxa),
+                            form=_lib.TAIL_HEADS, act=int(h.act))
+        grads = _operands(_lib.TailGrads, dict(dY1=dY1, dY2=dY2, dy3=dy3, dx=dx), ws=tuple(t.data_ptr() for t in ws),
+                          ws_bytes=tuple(t.numel() for t in ws))
+        w = _operands(_lib.TailWeights, dict(reads, pack=pack))
+        acts = _operands(_lib.TailActs, dict(zip(_TAIL_SAVED, saved)))
         with _timed("tail_bwd_fused"):
-            if rows is not None:
-                act, y, out2, bias, rs, dout = rows
-                for t, w in ((y, 512), (out2, 512), (dout, 512), (rs, 8)):
-                    assert t.shape == (M, w) and t.is_contiguous()
-                assert bias.is_contiguous() and bias.numel() == 512
-                _lib.check(self.lib.hicgat_tail_bwd_fused_rows(
-                    P(dcoords), M, P(Y1), P(st1), P(Y2), P(st2), P(y3), P(st3), *[P(t) for t in ts], P(dY1), P(dY2),
-                    P(dy3), *wsa, int(act), P(y), P(out2), P(bias), P(dout), P(rs), P(pack), _lib.stream(dev)),
-                    "hicgat_tail_bwd_fused_rows")
-            elif heads is None:
-                _lib.check(self.lib.hicgat_tail_bwd_fused(
-                    P(dcoords), M, P(Y1), P(st1), P(Y2), P(st2), P(y3), P(st3), *[P(t) for t in ts], P(dx), P(dY1),
-                    P(dY2), P(dy3), *wsa, P(pack), _lib.stream(dev)), "hicgat_tail_bwd_fused")
-            else:
-                h = heads
-                assert h.dout.shape == (M, 512) and h.dout.is_contiguous() and h.dxa.shape == (M, 1024)
-                assert h.dxa.is_contiguous() and h.rs.shape == (M, 8) and h.rs.is_contiguous()
-                _lib.check(self.lib.hicgat_tail_bwd_fused_heads(
-                    P(dcoords), M, P(Y1), P(st1), P(Y2), P(st2), P(y3), P(st3), *[P(t) for t in ts], P(dY1), P(dY2),
-                    P(dy3), *wsa, int(h.act), P(h.Y0), P(h.W), P(h.bias), P(h.dout), P(h.rs), P(h.dxa), P(pack),
-                    _lib.stream(dev)), "hicgat_tail_bwd_fused_heads")
+            _lib.check(self.lib.hicgat_tail_bwd(w, acts, P(dcoords), M, grads, gat, _lib.stream(dev)),
+                       "hicgat_tail_bwd")
         return dx, dY1, dY2, dy3, ws
 
     def tail_waves(self):
@@ -672,7 +679,7 @@ class HipKernels:
         return int(self.lib.hicgat_tail_bwd_waves())
 
     def tail_partial_rows(self, M):
-        """Rows of LayerNorm partials hicgat_tail_bwd_fused leaves per workspace: one per workgroup."""
+        """Rows of LayerNorm partials hicgat_tail_bwd leaves per workspace: one per workgroup."""
         return int(self.lib.hicgat_tail_bwd_partial_rows(M))
 
     # -- LayerNorm -> act (+ res) (-> LayerNorm) and the elementwise act (ln_act.hip) ---------------

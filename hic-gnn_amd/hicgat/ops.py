@@ -5,7 +5,9 @@
 * ``fused_dist_loss`` -- cdist + MSELoss (+ Pearson / combined loss value) fused (a7-a9), D never
                          materialised; returns the loss scalar and keeps the fp64 stats.
 """
+import collections
 import contextlib
+import operator
 import os
 
 import torch
@@ -36,7 +38,7 @@ def _dev_check(*ts):
 
 _ACTS = {None: 0, "relu": 1}
 # the single-GPU GATConv's gather-free rows pass (hicgat_gat_agg_bwd_rows) in the one-kernel tail
-# backward's epilogue when that tail consumes the layer's output (hicgat_tail_bwd_fused_rows); 0: the
+# backward's epilogue when that tail consumes the layer's output (hicgat_tail_bwd, HICGAT_TAIL_ROWS); 0: the
 # separate pass
 FUSE_ROWS = os.environ.get("HICGAT_FUSE_ROWS", "1") != "0"
 # the tail's weight pack written by the step's first launch (step_pack); 0: its own launch in the forward
@@ -83,7 +85,7 @@ class _GATConvFn(torch.autograd.Function):
             if FUSE_ROWS and (H, D // H) == (2, 256):
                 # (only this shape: the fused epilogue writes (2, 256)-layout row stats)
                 # the one-kernel tail that consumes ``out`` may run this layer's rows pass in its
-                # backward's epilogue (_FusedTailFn; hicgat_tail_bwd_fused_rows): it finds these
+                # backward's epilogue (_FusedTailFn; hicgat_tail_bwd, HICGAT_TAIL_ROWS): it finds these
                 # operands on ``out`` and records the dout it wrote in the shared state
                 ctx.rows_state = {"dout": None}
                 out._hicgat_rows = (act, out2, row_stats, b, ctx.rows_state)
@@ -782,7 +784,7 @@ def _dual_param_grads(K, W1, b1, W2, b2, dY, x):
 
 def _ln_param_grads(K, gamma, beta, ws, rows):
     """A LayerNorm's dgamma / dbeta = the column sums of the first ``rows`` per-workgroup partial rows
-    [dgamma | dbeta] that hicgat_tail_bwd_fused left in ``ws``: into the (adjacent) sinks as queued
+    [dgamma | dbeta] that hicgat_tail_bwd left in ``ws``: into the (adjacent) sinks as queued
     side work (ONE colsum launch over the live rows, its size as the lane-balancing work) or new
     tensors (returned)."""
     W = gamma.shape[0]
@@ -879,34 +881,50 @@ FUSED_TAIL_BWD = os.environ.get("HICGAT_FUSED_TAIL_BWD", "1") != "0"
 # forward; 0: the row-major weights)
 TAIL_PACK = os.environ.get("HICGAT_TAIL_PACK", "1") != "0"
 
+# The flagship tail's 18 parameters as (name, attribute path on the model), in the order ``_FusedTailFn``
+# takes them and returns their gradients
+TAIL_PARAMS = (("Wa", "densea.weight"), ("ba", "densea.bias"), ("Wal", "align_densea.weight"),
+               ("bal", "align_densea.bias"), ("ga", "norm_a.weight"), ("bea", "norm_a.bias"),
+               ("W1", "dense1.weight"), ("b1", "dense1.bias"), ("W1al", "align_dense1.weight"),
+               ("b1al", "align_dense1.bias"), ("g1", "norm1.weight"), ("be1", "norm1.bias"),
+               ("W2", "dense2.weight"), ("b2", "dense2.bias"), ("g2", "norm2.weight"), ("be2", "norm2.bias"),
+               ("W3", "dense3.weight"), ("b3", "dense3.bias"))
+_TailParams = collections.namedtuple("_TailParams", [name for name, _ in TAIL_PARAMS])
+
+
+def _tail_params(model):
+    return _TailParams(*(operator.attrgetter(path)(model) for _, path in TAIL_PARAMS))
+
 
 class _FusedTailFn(torch.autograd.Function):
     """models.py:638-659 after the relu (GATNetSelectiveResidualsUpdated.post_act): the forward in
-    one kernel (hicgat_tail_fwd_fused), which writes the tensors the per-layer autograd functions
+    one kernel (hicgat_tail_fwd), which writes the tensors the per-layer autograd functions
     would save; the backward runs those functions' own backward steps on them, in autograd's order
     (dense3, norm2, dense2, block 2, block 1), so its kernels, side-stream parameter gradients and
     sums are the per-layer path's."""
 
     @staticmethod
-    def forward(ctx, x, Wa, ba, Wal, bal, ga, bea, W1, b1, W1al, b1al, g1, be1, W2, b2, g2, be2, W3, b3, eps,
-                coords_out=None, heads=None, prepack=None):
+    def forward(ctx, x, *args):
+        p, (eps, coords_out, heads, prepack) = _TailParams(*args[:len(TAIL_PARAMS)]), args[len(TAIL_PARAMS):]
         K = kernels.default()
         x = x.contiguous()
-        W1c, b1c = _joined(Wa, Wal).contiguous(), _joined(ba, bal).contiguous()
-        W2c, b2c = _joined(W1, W1al).contiguous(), _joined(b1, b1al).contiguous()
+        # the kernels' operands, built once: the backward reads them from ctx
+        w = kernels.TailWeights(
+            W1c=_joined(p.Wa, p.Wal).contiguous(), b1c=_joined(p.ba, p.bal).contiguous(), g1=p.ga.contiguous(),
+            be1=p.bea.contiguous(), W2c=_joined(p.W1, p.W1al).contiguous(), b2c=_joined(p.b1, p.b1al).contiguous(),
+            g2=p.g1.contiguous(), be2=p.be1.contiguous(), W3=p.W2.contiguous(), b3=p.b2.contiguous(),
+            g3=p.g2.contiguous(), be3=p.be2.contiguous(), W4=p.W3.contiguous(), b4=p.b3.contiguous())
         # heads: x's rows are formed (written) by the kernel from the xagg GATConv's aggregates
         # the weights as packed copies for both kernels (made once per forward -- or by the training
         # step's first launch, ``prepack``: step_pack -- the backward reuses them)
         if prepack is not None:
             pack = prepack          # (heads: a pack with the heads' W, else the launch is refused)
         else:
-            pack = K.tail_pack(W1c, W2c, heads.W if heads is not None else None) if TAIL_PACK else None
-        coords, saved = K.tail_fwd_fused(x, W1c, b1c, ga.contiguous(), bea.contiguous(), W2c, b2c, g1.contiguous(),
-                                         be1.contiguous(), W2.contiguous(), b2.contiguous(), g2.contiguous(),
-                                         be2.contiguous(), W3.contiguous(), b3.contiguous(), eps, coords=coords_out,
-                                         heads=heads, pack=pack)
+            pack = K.tail_pack(w.W1c, w.W2c, heads.W if heads is not None else None) if TAIL_PACK else None
+        coords, saved = K.tail_fwd_fused(x, w, eps, coords=coords_out, heads=heads, pack=pack)
         ctx.heads = heads
         ctx.pack = pack
+        ctx.weights = w
         link = getattr(x, "_hicgat_rows", None) if heads is None else None
         # the GATConv's rows pass in this backward's epilogue: its relu output is exactly our input rows
         ctx.rows = link if (link is not None and FUSE_ROWS and K.tail_waves() == 16 and x.shape[1] == 512) else None
@@ -917,13 +935,13 @@ class _FusedTailFn(torch.autograd.Function):
             coords = torch.empty(0, dtype=coords_out.dtype, device=coords_out.device).set_(
                 coords_out.untyped_storage(), coords_out.storage_offset(), coords_out.shape, coords_out.stride())
         ctx.save_for_backward(x, *saved)
-        ctx.params = (Wa, ba, Wal, bal, ga, bea, W1, b1, W1al, b1al, g1, be1, W2, b2, g2, be2, W3, b3)
+        ctx.params = p
         return coords
 
     @staticmethod
     def backward(ctx, dcoords):
         x, Y1, st1, z1, Y2, st2, z2, y3, st3, z3 = ctx.saved_tensors
-        Wa, ba, Wal, bal, ga, bea, W1, b1, W1al, b1al, g1, be1, W2, b2, g2, be2, W3, b3 = ctx.params
+        p = ctx.params
         if FUSED_TAIL_BWD:
             # the input-gradient chain in one launch; the parameter gradients from its dY tensors
             # and LN partials, issued in the per-layer path's order (dense3, norm2, dense2, block 2,
@@ -935,31 +953,29 @@ class _FusedTailFn(torch.autograd.Function):
                 act, out2, rs, b, state = ctx.rows
                 dout = torch.empty((dc.shape[0], 512), dtype=torch.float32, device=dc.device)
                 rows = (act, x, out2, b, rs, dout)
-            dx, dY1, dY2, dy3, (ws1, ws2, ws3) = K.tail_bwd_fused(
-                dc, ctx.saved_tensors[1:], W3.contiguous(), W2.contiguous(), _joined(W1, W1al).contiguous(),
-                _joined(Wa, Wal).contiguous(), ga.contiguous(), bea.contiguous(), g1.contiguous(), be1.contiguous(),
-                g2.contiguous(), be2.contiguous(), heads=ctx.heads, pack=ctx.pack, rows=rows)
+            dx, dY1, dY2, dy3, (ws1, ws2, ws3) = K.tail_bwd_fused(dc, ctx.saved_tensors[1:], ctx.weights,
+                                                                  heads=ctx.heads, pack=ctx.pack, rows=rows)
             if rows is not None:
                 dx = dout               # the GATConv's backward finds it in the shared state and skips its rows pass
                 state["dout"] = dout
             rows = K.tail_partial_rows(dc.shape[0])   # the kernel's partial rows: one per workgroup
-            dW3, db3 = _wb_grad_to(K, W3, b3, dc, z3)
-            dg2, dbe2 = _ln_param_grads(K, g2, be2, ws3, rows)
-            dW2, db2 = _wb_grad_to(K, W2, b2, dy3, z2)
-            dg1, dbe1 = _ln_param_grads(K, g1, be1, ws2, rows)
-            dW1, db1, dW1al, db1al = _dual_param_grads(K, W1, b1, W1al, b1al, dY2, z1)
-            dga, dbea = _ln_param_grads(K, ga, bea, ws1, rows)
-            dWa, dba, dWal, dbal = _dual_param_grads(K, Wa, ba, Wal, bal, dY1, x)
+            dW3, db3 = _wb_grad_to(K, p.W3, p.b3, dc, z3)
+            dg2, dbe2 = _ln_param_grads(K, p.g2, p.be2, ws3, rows)
+            dW2, db2 = _wb_grad_to(K, p.W2, p.b2, dy3, z2)
+            dg1, dbe1 = _ln_param_grads(K, p.g1, p.be1, ws2, rows)
+            dW1, db1, dW1al, db1al = _dual_param_grads(K, p.W1, p.b1, p.W1al, p.b1al, dY2, z1)
+            dga, dbea = _ln_param_grads(K, p.ga, p.bea, ws1, rows)
+            dWa, dba, dWal, dbal = _dual_param_grads(K, p.Wa, p.ba, p.Wal, p.bal, dY1, x)
             return (dx if ctx.needs_input_grad[0] else None, dWa, dba, dWal, dbal, dga, dbea, dW1, db1, dW1al, db1al,
                     dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3, None, None, None, None)
         relu = (kernels.HipKernels.ACT_RELU, 0.0)
-        dz3, dW3, db3 = _linear_backward(W3, b3, z3, dcoords)
-        dy3, _, dg2, dbe2, _, _ = _ln_act_res_backward(relu, (g2, be2, None, None), False, y3, st3, None, None, dz3)
-        dz2, dW2, db2 = _linear_backward(W2, b2, z2, dy3)
+        dz3, dW3, db3 = _linear_backward(p.W3, p.b3, z3, dcoords)
+        dy3, _, dg2, dbe2, _, _ = _ln_act_res_backward(relu, (p.g2, p.be2, None, None), False, y3, st3, None, None, dz3)
+        dz2, dW2, db2 = _linear_backward(p.W2, p.b2, z2, dy3)
         dz1, dW1, db1, dW1al, db1al, dg1, dbe1, _, _ = _dual_ln_act_res_backward(
-            relu, (W1, b1, W1al, b1al, g1, be1, None, None), True, z1, Y2, st2, None, dz2)
+            relu, (p.W1, p.b1, p.W1al, p.b1al, p.g1, p.be1, None, None), True, z1, Y2, st2, None, dz2)
         dx, dWa, dba, dWal, dbal, dga, dbea, _, _ = _dual_ln_act_res_backward(
-            relu, (Wa, ba, Wal, bal, ga, bea, None, None), ctx.needs_input_grad[0], x, Y1, st1, None, dz1)
+            relu, (p.Wa, p.ba, p.Wal, p.bal, p.ga, p.bea, None, None), ctx.needs_input_grad[0], x, Y1, st1, None, dz1)
         return (dx, dWa, dba, dWal, dbal, dga, dbea, dW1, db1, dW1al, db1al, dg1, dbe1, dW2, db2, dg2, dbe2,
                 dW3, db3, None, None, None, None)
 
@@ -973,7 +989,7 @@ def fused_tail_ok(model, x):
 
 
 class TailHeads:
-    """The xagg GATConv's operands of the head-fused tail kernels (hicgat_tail_{fwd,bwd}_fused_heads):
+    """The xagg GATConv's operands of the head-fused tail kernels (hicgat_tail_{fwd,bwd}, HICGAT_TAIL_HEADS):
     X4 [2, 2, M, 512] (xa^h = X4[h, 0]), lin_l's weight W [512, 512] and bias [512], and the buffers
     they write: Y0 [M, 512] (the forward; the tail's input rows relu(Y0) go into ``fused_tail``'s x),
     dout [M, 512], the own rows' row stats rs [M, 8] and dxa [M, 1024] (the backward)."""
@@ -996,12 +1012,8 @@ def fused_tail(model, x, coords_out=None, heads=None):
     ``heads`` (``TailHeads``, ``tail_heads_ok`` first): x's rows are formed from the xagg GATConv's
     aggregates in the same launch (x is written), and the backward writes the GATConv's dout /
     delta / dxa instead of x's gradient."""
-    m = model
-    return _FusedTailFn.apply(x, m.densea.weight, m.densea.bias, m.align_densea.weight, m.align_densea.bias,
-                              m.norm_a.weight, m.norm_a.bias, m.dense1.weight, m.dense1.bias, m.align_dense1.weight,
-                              m.align_dense1.bias, m.norm1.weight, m.norm1.bias, m.dense2.weight, m.dense2.bias,
-                              m.norm2.weight, m.norm2.bias, m.dense3.weight, m.dense3.bias, m.norm_a.eps, coords_out,
-                              heads, getattr(m, "_hicgat_prepack", None))
+    return _FusedTailFn.apply(x, *_tail_params(model), model.norm_a.eps, coords_out, heads,
+                              getattr(model, "_hicgat_prepack", None))
 
 
 def step_pack(model, x):
@@ -1019,9 +1031,10 @@ def step_pack(model, x):
             and FUSED_TAIL_MIN_M <= x.shape[0] <= FUSED_TAIL_MAX_M
             and m.norm_a.eps == m.norm1.eps == m.norm2.eps):
         return None
-    if not (_adjacent(m.densea.weight, m.align_densea.weight) and _adjacent(m.dense1.weight, m.align_dense1.weight)):
+    p = _tail_params(m)
+    if not (_adjacent(p.Wa, p.Wal) and _adjacent(p.W1, p.W1al)):
         return None
-    W1c, W2c = _joined(m.densea.weight, m.align_densea.weight), _joined(m.dense1.weight, m.align_dense1.weight)
+    W1c, W2c = _joined(p.Wa, p.Wal), _joined(p.W1, p.W1al)
     buf = getattr(m, "_hicgat_pack_buf", None)
     if buf is None or buf.device != x.device:
         n = int(kernels.default().lib.hicgat_tail_pack_bytes())

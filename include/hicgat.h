@@ -628,41 +628,90 @@ int hicgat_act_fwd(const float *x, int M, int W, int act, float slope, float *y,
 int hicgat_act_bwd(const float *dy, const float *x, int M, int W, int act, float slope, float *dx,
                    hicgat_stream_t stream);
 
-/* ---- The flagship's MLP tail forward in one launch (tail_fused.hip; replaces the dual-Linear GEMMs,
+/* ---- The flagship's MLP tail in one launch per direction (tail_fused.hip; replaces the dual-Linear GEMMs,
  * LayerNorm row passes and Linear GEMMs of models.py:637-659 for GATNetSelectiveResidualsUpdated) ----
- * x [M][512] (ld ldx, 16-B aligned rows): the GATConv output after its relu.  W1c [512][512] = [W_densea;
- * W_align_densea], b1c [512]; g1/be1 [256] = norm_a; W2c [256][256] = [W_dense1; W_align_dense1], b2c
- * [256]; g2/be2 [128] = norm1; W3 [64][128] / b3 = dense2; g3/be3 [64] = norm2; W4 [3][64] / b4 = dense3.
- * Writes what the backward reads: Y1 [M][512] (block-1 GEMM + bias), st1 [M][2] (mean, rstd), z1
- * [M][256], Y2 [M][256], st2, z2 [M][128], y3 [M][64], st3, z3 [M][64], and coords [M][3].
- * 16 rows per workgroup, fp32 MFMA (16x16x4), LayerNorm eps inside the square root. */
-int hicgat_tail_fwd_fused(const float *x, int64_t ldx, int M, const float *W1c, const float *b1c, const float *g1,
-                          const float *be1, const float *W2c, const float *b2c, const float *g2, const float *be2,
-                          const float *W3, const float *b3, const float *g3, const float *be3, const float *W4,
-                          const float *b4, float eps, float *Y1, float *st1, float *z1, float *Y2, float *st2,
-                          float *z2, float *y3, float *st3, float *z3, float *coords, const void *pack,
-                          hicgat_stream_t stream);
-/* pack: NULL, or the packed weight copies hicgat_tail_pack made from THESE W1c / W2c (and, for the head
- * forms, Wh): the kernels then read W1c, W2c and Wh from it (1 KB contiguous per wave load instead of
- * 16 rows x 64 B: the vector memory path serves the row-major rows at 16 B per clock per CU, a quarter
- * of the contiguous rate, and that set the pace of the kernels' GEMM phases); results bitwise the
- * row-major form.  W3 / W4 are always read row-major.  hicgat_tail_pack_bytes(): the buffer's size.
- * Not a reference interface: the copies are a layout of the same parameters.  The library records,
- * per pack buffer, whether its last hicgat_tail_pack included Wh: the head-fused forms
- * (hicgat_tail_{fwd,bwd}_fused_heads) return HICGAT_EINVAL for a pack made with Wh = NULL. */
+ * The operands travel as four structs, passed by pointer and read completely before the call returns
+ * (the caller may free them right after it, also during a graph capture).  Each struct leads with the
+ * pointers both directions require; a NULL struct or required pointer, M < 0: HICGAT_EINVAL; M == 0:
+ * HICGAT_OK without a launch.
+ * hicgat_tail_weights: W1c [512][512] = [W_densea; W_align_densea], b1c [512]; g1/be1 [256] = norm_a; W2c
+ *   [256][256] = [W_dense1; W_align_dense1], b2c [256]; g2/be2 [128] = norm1; W3 [64][128] / b3 = dense2;
+ *   g3/be3 [64] = norm2; W4 [3][64] / b4 = dense3; eps: the LayerNorms' (inside the square root).  The
+ *   backward does not read b1c, b2c, b3, b4 and eps.  W1c, W2c, W3 and pack 16-B aligned (else
+ *   HICGAT_EUNSUPPORTED).
+ *   pack: NULL, or the packed weight copies hicgat_tail_pack made from THESE W1c / W2c (and, for HEADS,
+ *   Wh): the kernels then read W1c, W2c and Wh from it (1 KB contiguous per wave load instead of
+ *   16 rows x 64 B: the vector memory path serves the row-major rows at 16 B per clock per CU, a quarter
+ *   of the contiguous rate, and that set the pace of the kernels' GEMM phases); results bitwise the
+ *   row-major form.  W3 / W4 are always read row-major.  hicgat_tail_pack_bytes(): the buffer's size.
+ *   Not a reference interface: the copies are a layout of the same parameters.  The library records,
+ *   per pack buffer, whether its last hicgat_tail_pack included Wh: HEADS returns HICGAT_EINVAL for a
+ *   pack made with Wh = NULL.
+ * hicgat_tail_acts: what the forward writes for the backward: Y1 [M][512] (block-1 GEMM + bias), st1 [M][2]
+ *   (mean, rstd), Y2 [M][256], st2, y3 [M][64], st3 -- the backward reads these six -- and z1 [M][256],
+ *   z2 [M][128], z3 [M][64] (each block's output: the weight-gradient GEMMs' inputs). */
+typedef struct {
+  const float *W1c, *W2c, *W3, *W4, *g1, *be1, *g2, *be2, *g3, *be3;
+  const float *b1c, *b2c, *b3, *b4;
+  float eps;
+  const void *pack;
+} hicgat_tail_weights;
+typedef struct {
+  float *Y1, *st1, *Y2, *st2, *y3, *st3;
+  float *z1, *z2, *z3;
+} hicgat_tail_acts;
+/* hicgat_tail_grads (the backward writes): dY1 [M][512] = [dy | dres] of block 1, dY2 [M][256] of block 2, dy3
+ *   [M][64] (dense2's output gradient) -- the inputs of the weight-gradient GEMMs -- and each LayerNorm's
+ *   dgamma/dbeta partials into ws[0] / ws[1] / ws[2] (W = 256 / 128 / 64): rows [0, ceil(M/16)) of a [.][2W]
+ *   = [dgamma | dbeta] matrix, one per 16-row workgroup (its waves' partials added in wave order; the
+ *   rows' column sums, e.g. hicgat_colsum, are dgamma / dbeta); ws_bytes[i] at least
+ *   hicgat_tail_bwd_workspace_bytes(M, W) (else HICGAT_EINVAL).  dx [M][512], the gradient of the tail's
+ *   input: required by the plain form, not read by the others. */
+typedef struct {
+  float *dY1, *dY2, *dy3;
+  void *ws[3];
+  float *dx;
+  size_t ws_bytes[3];
+} hicgat_tail_grads;
+/* hicgat_tail_gat: the GATConv side of the fused forms (a NULL struct: HICGAT_TAIL_PLAIN, which reads no
+ * other field; an unknown form: HICGAT_EINVAL).
+ * HICGAT_TAIL_HEADS, for the sharded aggregate-first GATConv (hicgat.dist "xagg"; the GATConv of
+ *   models.py:619 by linearity per head, then the tail): the forward forms the tail's input rows
+ *   itself, Y0[:, 256h:256h+256] = xa^h W_h^T + b^h (xa^h = x + h * xa_head_stride, [M][ldx], a multiple
+ *   of 4; W_h = rows 256h.. of lin_l's weight Wh [512][512]; bh [512]) and O = relu(Y0) (both [M][512],
+ *   written), replacing the per-head GEMM launches and their slab sum.  The backward, instead of writing
+ *   dx, runs the GATConv's rows backward and its input-gradient GEMM: dout = dx * (Y0 > 0) (act != 0;
+ *   act = 0: dout = dx) into dout [M][512], delta^h = <dout^h, Y0^h - b^h> into row_stats[8r + 4 + h] (its
+ *   [4:6] S3 values move to [6:8], as hicgat_xagg_rows_bwd does), dxa [M][1024] = [dout^0 W_0 | dout^1
+ *   W_1].  Needs hicgat_tail_bwd_waves() >= 8 (else HICGAT_EUNSUPPORTED); out2 is not read.
+ * HICGAT_TAIL_ROWS, a form of the backward only (hicgat_tail_fwd: HICGAT_EINVAL), for the single-GPU
+ *   GATConv: its gather-free rows pass in the epilogue (hicgat_gat_agg_bwd_rows on the dx rows while they
+ *   are in LDS, same arithmetic, bitwise): no dx is written; dout [M][512] = dx [Y0 > 0] (act != 0) or dx,
+ *   and row_stats[8i + 4 .. 8i + 8) = (delta, da_dst) from the forward's S3 there, for Y0 = the GATConv's
+ *   relu output (the tail's input rows), out2 and bh = bias of hicgat_gat_agg_fwd.  One row per wave:
+ *   HICGAT_EUNSUPPORTED unless hicgat_tail_bwd_waves() == 16; Wh, O and dxa are not read.
+ * Wh, Y0, O (forward) and Y0, bh, dout, row_stats, out2 (backward) 16-B aligned (else HICGAT_EUNSUPPORTED). */
+#define HICGAT_TAIL_PLAIN 0
+#define HICGAT_TAIL_HEADS 1
+#define HICGAT_TAIL_ROWS 2
+typedef struct {
+  int form, act;
+  int64_t xa_head_stride;
+  const float *Wh, *bh;
+  float *Y0, *O;
+  const float *out2;
+  float *dout, *row_stats, *dxa;
+} hicgat_tail_gat;
+/* Forward: x [M][512] (ld ldx >= 512, a multiple of 4, 16-B aligned rows) is the GATConv output after its
+ * relu -- for HEADS the aggregates xa (ld ldx), see above; writes acts and coords [M][3].  16 rows per
+ * workgroup, fp32 MFMA (16x16x4). */
+int hicgat_tail_fwd(const hicgat_tail_weights *weights, const float *x, int64_t ldx, int M,
+                    const hicgat_tail_acts *acts, float *coords, const hicgat_tail_gat *gat, hicgat_stream_t stream);
 size_t hicgat_tail_pack_bytes(void);
 int hicgat_tail_pack(const float *W1c, const float *W2c, const float *Wh, void *pack, size_t pack_bytes,
                      hicgat_stream_t stream);
-/* The same tail's backward input-gradient chain in one launch: from dcoords [M][3] and the forward's
- * Y1, st1, Y2, st2, y3, st3 (hicgat_tail_fwd_fused), with W4 = dense3.weight [3][64], W3 = dense2.weight
- * [64][128], W2c = [W_dense1; W_align_dense1] [256][256], W1c = [W_densea; W_align_densea] [512][512],
- * g1/be1 = norm_a, g2/be2 = norm1, g3/be3 = norm2: writes dx [M][512] (the gradient of the tail's
- * input), dY1 [M][512] = [dy | dres] of block 1, dY2 [M][256] of block 2, dy3 [M][64] (dense2's output
- * gradient) -- the inputs of the weight-gradient GEMMs -- and each LayerNorm's dgamma/dbeta partials
- * into ws1 / ws2 / ws3: rows
- * [0, ceil(M/16)) of a [.][2W] = [dgamma | dbeta] matrix, one per 16-row workgroup (its waves'
- * partials added in wave order; the rows' column sums, e.g. hicgat_colsum, are dgamma / dbeta); each
- * workspace at least hicgat_tail_bwd_workspace_bytes(M, W) for W = 256 / 128 / 64.
+/* Backward: the input-gradient chain from dcoords [M][3] and the forward's acts; writes grads (and, by
+ * gat's form, dout / row_stats / dxa instead of dx).
  * hicgat_tail_bwd_waves(): the waves per workgroup of both tail kernels.
  * hicgat_tail_bwd_partial_rows(M): the rows of partials each workspace holds after the call, one per
  * workgroup (ceil(M / the kernel's row block); 0 for M <= 0) -- what the caller's column sums read.
@@ -670,49 +719,8 @@ int hicgat_tail_pack(const float *W1c, const float *W2c, const float *Wh, void *
 int hicgat_tail_bwd_waves(void);
 int hicgat_tail_bwd_partial_rows(int M);
 size_t hicgat_tail_bwd_workspace_bytes(int M, int W);
-int hicgat_tail_bwd_fused(const float *dcoords, int M, const float *Y1, const float *st1, const float *Y2,
-                          const float *st2, const float *y3, const float *st3, const float *W4, const float *W3,
-                          const float *W2c, const float *W1c, const float *g1, const float *be1, const float *g2,
-                          const float *be2, const float *g3, const float *be3, float *dx, float *dY1, float *dY2,
-                          float *dy3, void *ws1, size_t ws1_bytes, void *ws2, size_t ws2_bytes, void *ws3,
-                          size_t ws3_bytes, const void *pack, hicgat_stream_t stream);
-/* The head-fused forms for the sharded aggregate-first GATConv (hicgat.dist "xagg"; the GATConv of
- * models.py:619 by linearity per head, then the tail): the forward forms the tail's input rows
- * itself, Y0[:, 256h:256h+256] = xa^h W_h^T + b^h (xa^h = xa + h * xa_head_stride, [M][ld_xa]; W_h =
- * rows 256h.. of lin_l's weight Wh [512][512]; bh [512]) and O = relu(Y0) (both [M][512], written),
- * replacing the per-head GEMM launches and their slab sum; then the tail as hicgat_tail_fwd_fused.
- * The backward runs the chain of hicgat_tail_bwd_fused and, instead of writing dx, the GATConv's rows
- * backward and its input-gradient GEMM: dout = dx * (Y0 > 0) (act = 1; act = 0: dout = dx) into
- * dout [M][512], delta^h = <dout^h, Y0^h - b^h> into row_stats[8r + 4 + h] (its [4:6] S3 values move
- * to [6:8], as hicgat_xagg_rows_bwd does), dxa [M][1024] = [dout^0 W_0 | dout^1 W_1].  Both need
- * hicgat_tail_bwd_waves() == 8 (else HICGAT_EUNSUPPORTED). */
-int hicgat_tail_fwd_fused_heads(const float *xa, int64_t ld_xa, int64_t xa_head_stride, const float *Wh,
-                                const float *bh, float *Y0, float *O, int M, const float *W1c, const float *b1c,
-                                const float *g1, const float *be1, const float *W2c, const float *b2c, const float *g2,
-                                const float *be2, const float *W3, const float *b3, const float *g3, const float *be3,
-                                const float *W4, const float *b4, float eps, float *Y1, float *st1, float *z1,
-                                float *Y2, float *st2, float *z2, float *y3, float *st3, float *z3, float *coords,
-                                const void *pack, hicgat_stream_t stream);
-int hicgat_tail_bwd_fused_heads(const float *dcoords, int M, const float *Y1, const float *st1, const float *Y2,
-                                const float *st2, const float *y3, const float *st3, const float *W4, const float *W3,
-                                const float *W2c, const float *W1c, const float *g1, const float *be1, const float *g2,
-                                const float *be2, const float *g3, const float *be3, float *dY1, float *dY2,
-                                float *dy3, void *ws1, size_t ws1_bytes, void *ws2, size_t ws2_bytes, void *ws3,
-                                size_t ws3_bytes, int act, const float *Y0, const float *Wh, const float *bh,
-                                float *dout, float *row_stats, float *dxa, const void *pack, hicgat_stream_t stream);
-/* The plain tail's backward with the single-GPU GATConv's gather-free rows pass in its epilogue
- * (hicgat_gat_agg_bwd_rows on the dx rows while they are in LDS, same arithmetic, bitwise): no dx is
- * written; dout [M][512] = dx [y > 0] (act != 0) or dx, and row_stats[8i + 4 .. 8i + 8) = (delta,
- * da_dst) from the forward's S3 there, for y = the GATConv's relu output (the tail's input rows),
- * out2 and bias of hicgat_gat_agg_fwd.  One row per wave: HICGAT_EUNSUPPORTED unless the kernels
- * run 16 waves (hicgat_tail_bwd_waves). */
-int hicgat_tail_bwd_fused_rows(const float *dcoords, int M, const float *Y1, const float *st1, const float *Y2,
-                               const float *st2, const float *y3, const float *st3, const float *W4, const float *W3,
-                               const float *W2c, const float *W1c, const float *g1, const float *be1, const float *g2,
-                               const float *be2, const float *g3, const float *be3, float *dY1, float *dY2,
-                               float *dy3, void *ws1, size_t ws1_bytes, void *ws2, size_t ws2_bytes, void *ws3,
-                               size_t ws3_bytes, int act, const float *y, const float *out2, const float *bias,
-                               float *dout, float *row_stats, const void *pack, hicgat_stream_t stream);
+int hicgat_tail_bwd(const hicgat_tail_weights *weights, const hicgat_tail_acts *acts, const float *dcoords, int M,
+                    const hicgat_tail_grads *grads, const hicgat_tail_gat *gat, hicgat_stream_t stream);
 
 /* ---- f1: SAGEConv of the baseline model Net (layers.py:41-79, models.py:14-55) ----------------
  * hicgat_sage_weights: the float32 edge weight w of every entry of the (set_diag'd) device CSR --

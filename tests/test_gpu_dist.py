@@ -411,7 +411,7 @@ def test_world1_step_matches_float64_standin(mode, n):
 
 @pytest.mark.parametrize("n,world", [(3000, 1), (3000, 2)])
 def test_xagg_head_fused_tail_matches_separate_launches(n, world):
-    """The head-fused tail kernels (hicgat_tail_{fwd,bwd}_fused_heads: the xagg GATConv's per-head
+    """The head-fused tail kernels (hicgat_tail_{fwd,bwd} with HICGAT_TAIL_HEADS: the xagg GATConv's per-head
     GEMMs + bias / relu before the tail, its rows backward and dxa GEMMs after the tail's backward)
     against the separate launches (grouped row GEMMs, xagg_rows_bwd), rank 0 of ``world`` simulated
     ranks, two eager steps and two graph replays: the same loss to 1e-6, gradients to 1e-5 of their

@@ -1533,11 +1533,10 @@ def test_tail_pack_layout_and_bitwise_kernels():
             if heads:
                 h = ops.TailHeads(X4, Wh, bias, torch.empty(M, 512, **f), torch.empty(M, 512, **f),
                                   rs_init.clone(), torch.empty(M, 1024, **f), act=1)
-            coords, saved = K.tail_fwd_fused(xin, W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4, 1e-5,
-                                             heads=h, pack=pk)
+            tw = kernels.TailWeights(W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4)
+            coords, saved = K.tail_fwd_fused(xin, tw, 1e-5, heads=h, pack=pk)
             rs0 = h.rs.clone() if heads else None
-            dx, dY1, dY2, dy3, ws = K.tail_bwd_fused(dc, saved, W4, W3, W2c, W1c, g1, be1, g2, be2, g3, be3, heads=h,
-                                                     pack=pk)
+            dx, dY1, dY2, dy3, ws = K.tail_bwd_fused(dc, saved, tw, heads=h, pack=pk)
             torch.cuda.synchronize()
             o = [coords, *saved, dY1, dY2, dy3, *ws]
             if heads:
@@ -1624,7 +1623,7 @@ def test_fused_tail_matches_per_layer_path(monkeypatch, m, sinks, bwd):
 @pytest.mark.parametrize("n,graphed", [(3000, False), (3000, True), (20000, False)])
 def test_rows_pass_fused_into_tail_backward_is_bitwise(monkeypatch, n, graphed):
     """The single-GPU GATConv's rows pass (dout = g relu'(y), delta, da_dst; hicgat_gat_agg_bwd_rows)
-    run in the one-kernel tail backward's epilogue (hicgat_tail_bwd_fused_rows, ops.FUSE_ROWS) against
+    run in the one-kernel tail backward's epilogue (hicgat_tail_bwd with HICGAT_TAIL_ROWS, ops.FUSE_ROWS) against
     the separate pass: two training steps (eager, or captured and replayed) give the same loss,
     gradients and parameters bit for bit (same arithmetic on the same dx values)."""
     import hicgat
@@ -1718,7 +1717,7 @@ def test_persistent_tail_forward_is_bitwise_the_tile_grid(M):
     g1, g2, g3 = 1 + g1, 1 + g2, 1 + g3
     W3, W4, b4 = torch.randn(64, 128, **f) * 0.1, torch.randn(3, 64, **f) * 0.1, torch.randn(3, **f) * 0.1
     x = torch.relu(torch.randn(M, 512, **f))
-    args = (W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4, 1e-5)
+    args = (kernels.TailWeights(W1c, b1c, g1, be1, W2c, b2c, g2, be2, W3, b3, g3, be3, W4, b4), 1e-5)
     for pk in (None, K.tail_pack(W1c, W2c)):
         coords, saved = K.tail_fwd_fused(x, *args, pack=pk)
         parts = [K.tail_fwd_fused(x[r0:r0 + 4096], *args, pack=pk) for r0 in range(0, M, 4096)]

@@ -79,6 +79,11 @@ class Inputs:
             assert torch.equal(_bits(v), self.before[k]), (what, "input changed", k)
 
 
+def _addr(t):
+    """A tensor's address for a field of the C ABI's operand structs (None: NULL)."""
+    return None if t is None else t.data_ptr()
+
+
 def _pack(P, heads):
     _lib = _L()
     lib = _lib.lib()
@@ -129,17 +134,19 @@ def _run_forward(M, small, heads, ldx, use_pack):
     I = Inputs(**ins)
     out = {k: Guarded(M, c) for k, c in FWD_OUT + ((("Y0", 512), ("O", 512)) if heads else ())}
     pack = _pack(I, heads) if use_pack else None
-    tail = [R.EPS32] + [p(out[k].t) for k, _ in FWD_OUT] + [p(pack), _lib.stream(out["Y1"].buf.device)]
+    w = _lib.TailWeights(eps=R.EPS32, pack=_addr(pack), **{k: _addr(I[k]) for k in WKEYS})
+    acts = _lib.TailActs(**{k: _addr(out[k].t) for k, _ in FWD_OUT if k != "coords"})
     if heads:
         xa = I["X4"][:, :, :M]                        # head stride 2 (M + 5) 512, not 2 M 512
         assert xa.stride(0) != 2 * M * 512 and xa.stride(2) == 512
-        _lib.check(lib.hicgat_tail_fwd_fused_heads(p(xa), xa.stride(2), xa.stride(0), p(I["Wh"]), p(I["bh"]),
-                                                   p(out["Y0"].t), p(out["O"].t), M, *[p(I[k]) for k in WKEYS],
-                                                   *tail), "hicgat_tail_fwd_fused_heads")
+        xv, ld = xa, xa.stride(2)
+        gat = _lib.TailGat(form=_lib.TAIL_HEADS, xa_head_stride=xa.stride(0), Wh=_addr(I["Wh"]), bh=_addr(I["bh"]),
+                           Y0=_addr(out["Y0"].t), O=_addr(out["O"].t))
     else:
-        xv = I["xbuf"][:, :512]
-        _lib.check(lib.hicgat_tail_fwd_fused(p(xv), xv.stride(0), M, *[p(I[k]) for k in WKEYS], *tail),
-                   "hicgat_tail_fwd_fused")
+        xv, gat = I["xbuf"][:, :512], None
+        ld = xv.stride(0)
+    _lib.check(lib.hicgat_tail_fwd(w, p(xv), ld, M, acts, p(out["coords"].t), gat,
+                                   _lib.stream(out["Y1"].buf.device)), "hicgat_tail_fwd")
     torch.cuda.synchronize()
     what = ("fwd", M, small, heads, use_pack)
     for k, g in out.items():
@@ -174,7 +181,7 @@ def _forward_case(M, small=False, heads=False):
 
 @pytest.mark.parametrize("M", MS + ("persist",))
 def test_forward_stages(M):
-    """hicgat_tail_fwd_fused; ``persist``: M = 16 CUs + 1, the smallest grid of more than one round,
+    """hicgat_tail_fwd, the plain form; ``persist``: M = 16 CUs + 1, the smallest grid of more than one round,
     which takes the persistent kernel (its second tile per workgroup arrives by LDS-DMA)."""
     if M == "persist":
         M = 16 * torch.cuda.get_device_properties(0).multi_processor_count + 1
@@ -195,7 +202,7 @@ def _need_waves(n, exact=False):
 
 @pytest.mark.parametrize("M", MS)
 def test_forward_heads_stages(M):
-    """hicgat_tail_fwd_fused_heads: Y0, O = relu(Y0) and the tail on O."""
+    """hicgat_tail_fwd with HICGAT_TAIL_HEADS: Y0, O = relu(Y0) and the tail on O."""
     _need_waves(8)
     _forward_case(M, heads=True)
 
@@ -215,32 +222,32 @@ def _run_backward(M, zero_row, form, act, use_pack):
     I = Inputs(**ins)
     out = {k: Guarded(M, c) for k, c in BWD_OUT}
     nt = -(-M // 16)
-    wsa = []
+    ws, ws_bytes = [], []
     for i, W in (("1", 256), ("2", 128), ("3", 64)):
         g = out["p" + i] = Guarded(nt, 2 * W)
         nbytes = int(lib.hicgat_tail_bwd_workspace_bytes(M, W))
         assert nbytes == g.t.numel() * 4              # exactly the size the library asks for
-        wsa += [p(g.t), nbytes]
+        ws.append(_addr(g.t))
+        ws_bytes.append(nbytes)
     pack = _pack(I, form == "heads") if use_pack else None
-    head = [p(I["dc"]), M, p(I["Y1"]), p(I["st1"]), p(I["Y2"]), p(I["st2"]), p(I["y3"]), p(I["st3"])]
-    head += [p(I[k]) for k in BKEYS]
-    dys = [p(out["dY1"].t), p(out["dY2"].t), p(out["dy3"].t)]
-    s = _lib.stream(out["dY1"].buf.device)
+    w = _lib.TailWeights(pack=_addr(pack), **{k: _addr(I[k]) for k in BKEYS})      # b*, eps: not read
+    acts = _lib.TailActs(**{k: _addr(I[k]) for k in ("Y1", "st1", "Y2", "st2", "y3", "st3")})      # nor z*
+    grads = _lib.TailGrads(ws=tuple(ws), ws_bytes=tuple(ws_bytes), **{k: _addr(out[k].t) for k, _ in BWD_OUT})
     if form == "plain":
         out["dx"] = Guarded(M, 512)
-        _lib.check(lib.hicgat_tail_bwd_fused(*head, p(out["dx"].t), *dys, *wsa, p(pack), s), "hicgat_tail_bwd_fused")
+        grads.dx, gat = _addr(out["dx"].t), None
     else:
         out["dout"] = Guarded(M, 512)
         out["rs"] = Guarded(M, 8, init=B["rs"])
+        gat = _lib.TailGat(act=act, Y0=_addr(I["y"]), bh=_addr(I["bh"]), dout=_addr(out["dout"].t),
+                           row_stats=_addr(out["rs"].t))
         if form == "rows":
-            _lib.check(lib.hicgat_tail_bwd_fused_rows(*head, *dys, *wsa, act, p(I["y"]), p(I["out2"]), p(I["bh"]),
-                                                      p(out["dout"].t), p(out["rs"].t), p(pack), s),
-                       "hicgat_tail_bwd_fused_rows")
+            gat.form, gat.out2 = _lib.TAIL_ROWS, _addr(I["out2"])
         else:
             out["dxa"] = Guarded(M, 1024)
-            _lib.check(lib.hicgat_tail_bwd_fused_heads(*head, *dys, *wsa, act, p(I["y"]), p(I["Wh"]), p(I["bh"]),
-                                                       p(out["dout"].t), p(out["rs"].t), p(out["dxa"].t), p(pack), s),
-                       "hicgat_tail_bwd_fused_heads")
+            gat.form, gat.Wh, gat.dxa = _lib.TAIL_HEADS, _addr(I["Wh"]), _addr(out["dxa"].t)
+    _lib.check(lib.hicgat_tail_bwd(w, acts, p(I["dc"]), M, grads, gat, _lib.stream(out["dY1"].buf.device)),
+               "hicgat_tail_bwd")
     torch.cuda.synchronize()
     what = ("bwd", form, M, zero_row, act, use_pack)
     for k, g in out.items():
@@ -286,7 +293,7 @@ def _backward_case(M, form, act=0, zero_row=False):
 
 @pytest.mark.parametrize("M", MS)
 def test_backward_stages(M):
-    """hicgat_tail_bwd_fused: dy3, dY2, dY1, dx and the LayerNorm partial rows."""
+    """hicgat_tail_bwd, the plain form: dy3, dY2, dY1, dx and the LayerNorm partial rows."""
     _backward_case(M, "plain")
 
 
@@ -299,7 +306,7 @@ def test_backward_stages_pre_exactly_zero():
 @pytest.mark.parametrize("act", [0, 1])
 @pytest.mark.parametrize("M", MS)
 def test_backward_rows_epilogue(M, act):
-    """hicgat_tail_bwd_fused_rows: the chain, dout and row_stats[:, 4:8] against fp64, and dout /
+    """hicgat_tail_bwd with HICGAT_TAIL_ROWS: the chain, dout and row_stats[:, 4:8] against fp64, and dout /
     row_stats[:, 4:8] bitwise hicgat_gat_agg_bwd_rows on the plain form's dx (the kernel's claim)."""
     _need_waves(16, exact=True)
     o = _backward_case(M, "rows", act)
@@ -323,6 +330,6 @@ def test_backward_rows_epilogue(M, act):
 @pytest.mark.parametrize("act", [0, 1])
 @pytest.mark.parametrize("M", MS)
 def test_backward_heads_epilogue(M, act):
-    """hicgat_tail_bwd_fused_heads: the chain, dout, delta, the moved S3 and dxa."""
+    """hicgat_tail_bwd with HICGAT_TAIL_HEADS: the chain, dout, delta, the moved S3 and dxa."""
     _need_waves(8)
     _backward_case(M, "heads", act)

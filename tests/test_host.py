@@ -82,7 +82,9 @@ def test_ctypes_signatures_match_header_types():
     scalars = {"int": _lib.c_int, "int64_t": _lib.c_i64, "float": _lib.c_f, "double": _lib.c_d,
                "size_t": _lib.c_sz, "uint64_t": _lib.c_u64, "uint32_t": _lib.c_u32, "hicgat_stream_t": _lib.c_p}
     typed_pointers = {"hicgat_stream_t *": ctypes.POINTER(_lib.c_p), "hicgat_wgrad_job *": _lib.c_wjobs,
-                      "hicgat_colsum_job *": _lib.c_cjobs, "hicgat_gemm_job *": _lib.c_gjobs}
+                      "hicgat_colsum_job *": _lib.c_cjobs, "hicgat_gemm_job *": _lib.c_gjobs,
+                      "hicgat_tail_weights *": _lib.c_tailw, "hicgat_tail_acts *": _lib.c_taila,
+                      "hicgat_tail_grads *": _lib.c_tailg, "hicgat_tail_gat *": _lib.c_tailgat}
     data = {"void", "float", "double", "int32_t", "uint32_t", "int64_t", "uint8_t", "unsigned long long"}
 
     def expected(t, ret=False):
