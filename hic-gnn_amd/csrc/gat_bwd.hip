@@ -199,65 +199,40 @@ __global__ __launch_bounds__(256) void param_grad_stage2(const float *__restrict
 // the round-robin order, the DROP form and the other shapes are unmeasured and launch without it.
 constexpr size_t kSrcOccLds = 32768;
 
-// The gather half of hicgat_gat_agg_bwd_src_tiled (gat_tiles.hip): the sparse remainder's shares.
-int agg_bwd_src_split_launch(const int *rowptr_s, const int *col_s, int row_begin, int row_end, const float *h,
-                             const float *a_src, const float *a_dst, const float *row_stats, int64_t ldr,
-                             const float *dout, int64_t ldq4, float ns, float *dh, float *da_src, hipStream_t s) {
-  hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<true>), dim3((row_end - row_begin + 3) / 4), dim3(256), 0, s,
-                     rowptr_s, col_s, row_begin, row_end, h, a_src, a_dst, row_stats, ldr, dout, ldq4, nullptr, nullptr,
-                     ns, dh, da_src);
+// The gather half of the source pass's tiled form (gat_tiles.hip): the sparse remainder's shares.
+int agg_bwd_src_split_launch(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const hicgat_gat_tiles &t,
+                             const SrcArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<true>), dim3((g.row_end - g.row_begin + 3) / 4), dim3(256), 0, s,
+                     t.rowptr_s, t.col_s, g.row_begin, g.row_end, f.h, f.a_src, f.a_dst, a.row_stats, a.ldr, a.dout,
+                     a.ldq4, nullptr, nullptr, f.neg_slope, a.dh, a.da_src);
   HICGAT_CHECK_LAUNCH();
   return HICGAT_OK;
 }
 
 // The source pass's one launch: REMAP = remap, DROP = a mask given.
 template <class... MK>
-int agg_bwd_src_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end, const float *h,
-                       const float *a_src, const float *a_dst, const float *row_stats, int64_t ldr, const float *dout,
-                       int64_t ldq4, const float *att_s, const float *att_d, float ns, float *dh, float *da_src,
-                       bool remap, hipStream_t s, MK... mk) {
-  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
-  return for_gat_shape(H, C, [&](auto shape) {
+int agg_bwd_src_launch(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const SrcArgs &a, bool remap,
+                       hipStream_t s, MK... mk) {
+  const dim3 grid((g.row_end - g.row_begin + 3) / 4), block(256);
+  return for_gat_shape(f.H, f.C, [&](auto shape) {
     return with_flags(
         [&](auto rm) {
           using S = decltype(shape);
           constexpr bool REMAP = rm.value;
           if constexpr (S::h2c256)
             hipLaunchKernelGGL((agg_bwd_src_h2c256_kernel<false, REMAP, MK...>), grid, block,
-                               REMAP && !sizeof...(MK) ? kSrcOccLds : 0, s, rowptr, col, row_begin, row_end, h, a_src,
-                               a_dst, row_stats, ldr, dout, ldq4, att_s, att_d, ns, dh, da_src, mk...);
+                               REMAP && !sizeof...(MK) ? kSrcOccLds : 0, s, g.rowptr, g.col, g.row_begin, g.row_end,
+                               f.h, f.a_src, f.a_dst, a.row_stats, a.ldr, a.dout, a.ldq4, a.att_s, a.att_d,
+                               f.neg_slope, a.dh, a.da_src, mk...);
           else
-            hipLaunchKernelGGL((agg_bwd_src_generic_kernel<S::H, S::C, REMAP, MK...>), grid, block, 0, s, rowptr, col,
-                               row_begin, row_end, h, a_src, a_dst, row_stats, ldr, dout, ldq4, att_s, att_d, ns, dh,
-                               da_src, mk...);
+            hipLaunchKernelGGL((agg_bwd_src_generic_kernel<S::H, S::C, REMAP, MK...>), grid, block, 0, s, g.rowptr,
+                               g.col, g.row_begin, g.row_end, f.h, f.a_src, f.a_dst, a.row_stats, a.ldr, a.dout, a.ldq4,
+                               a.att_s, a.att_d, f.neg_slope, a.dh, a.da_src, mk...);
           HICGAT_CHECK_LAUNCH();
           return HICGAT_OK;
         },
         remap);
   });
-}
-
-// What hicgat_gat_agg_bwd_src and hicgat_gat_agg_drop_bwd_src check and do; mk: NULL without dropout.
-// HICGAT_SRC_ROUND_ROBIN turns the XCD remap off.
-static int agg_bwd_src_checked(const int32_t *rowptr, const int32_t *col, int N, int H, int C, int row_begin,
-                               int row_end, const float *h, const float *a_src, const float *a_dst,
-                               const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
-                               const float *att_src, const float *att_dst, float neg_slope, float *dh, float *da_src,
-                               int flags, const AttnMaskArgs *mk, hipStream_t s) {
-  if (flags & ~HICGAT_SRC_ROUND_ROBIN) return HICGAT_EINVAL;
-  const bool remap = !(flags & HICGAT_SRC_ROUND_ROBIN);
-  if (N < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
-  if (ld_stats < 4 * H || ld_stats % 4 || ld_dout < H * C || ld_dout % 4) return HICGAT_EINVAL;
-  if (row_end == row_begin) return HICGAT_OK;
-  if (!rowptr || !col || !h || !a_src || !a_dst || !row_stats || !dout || !att_src || !att_dst ||
-      !dh || !da_src)
-    return HICGAT_EINVAL;
-  if (mk)
-    return agg_bwd_src_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
-                              ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, remap, s, *mk);
-  return agg_bwd_src_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
-                            ld_dout / 4, att_src, att_dst, neg_slope, dh, da_src, remap, s);
 }
 
 }  // namespace hicgat
@@ -287,29 +262,32 @@ extern "C" int hicgat_gat_agg_bwd_dst(const int32_t *rowptr, const int32_t *col,
   });
 }
 
-extern "C" int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H,
-                                      int C, int row_begin, int row_end, const float *h,
-                                      const float *a_src, const float *a_dst,
-                                      const float *row_stats, int64_t ld_stats, const float *dout,
-                                      int64_t ld_dout, const float *att_src, const float *att_dst,
-                                      float neg_slope, float *dh, float *da_src, int flags,
+// The rules of every form, in the order of include/hicgat.h; the tiled form's own follow in agg_bwd_src_tiled,
+// which reads the remainder's CSR in place of the graph's.  HICGAT_SRC_ROUND_ROBIN turns the XCD remap off.
+extern "C" int hicgat_gat_agg_bwd_src(const hicgat_gat_graph *graph, const hicgat_gat_feats *feats,
+                                      const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
+                                      const float *att_src, const float *att_dst, float *dh, float *da_src, int flags,
+                                      const hicgat_attn_drop *drop, const hicgat_gat_tiles *tiles,
                                       hicgat_stream_t stream) {
-  return agg_bwd_src_checked(rowptr, col, N, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
-                             ld_dout, att_src, att_dst, neg_slope, dh, da_src, flags, nullptr, (hipStream_t)stream);
-}
-
-// ---- attention dropout: hicgat_gat_agg_bwd_src with the forward's keep factors recomputed ---------
-extern "C" int hicgat_gat_agg_drop_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H, int C,
-                                           int row_begin, int row_end, const float *h, const float *a_src,
-                                           const float *a_dst, const float *row_stats, int64_t ld_stats,
-                                           const float *dout, int64_t ld_dout, const float *att_src,
-                                           const float *att_dst, float neg_slope, float *dh, float *da_src,
-                                           int flags, double p, uint64_t seed, const int64_t *step_counter,
-                                           int64_t step_value, uint32_t site, hicgat_stream_t stream) {
-  if (!p_ok(p) || !attn_site_ok(site) || misaligned(step_counter, 8)) return HICGAT_EINVAL;
-  const AttnMaskArgs mk = attn_mask_args(p, seed, step_counter, step_value, site);
-  return agg_bwd_src_checked(rowptr, col, N, H, C, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
-                             ld_dout, att_src, att_dst, neg_slope, dh, da_src, flags, &mk, (hipStream_t)stream);
+  if (!graph || !feats || (drop && tiles)) return HICGAT_EINVAL;
+  if (drop && !attn_drop_ok(*drop)) return HICGAT_EINVAL;
+  if ((flags & ~HICGAT_SRC_ROUND_ROBIN) || (flags && tiles)) return HICGAT_EINVAL;
+  const hicgat_gat_graph &g = *graph;
+  const hicgat_gat_feats &f = *feats;
+  if (g.N < 0 || g.row_begin < 0 || g.row_end > g.N || g.row_begin > g.row_end || (tiles && tiles->ntiles < 0))
+    return HICGAT_EINVAL;
+  if (tiles ? f.H != 2 || f.C != 256 : !gat_shape_supported(f.H, f.C)) return HICGAT_EUNSUPPORTED;
+  if (ld_stats < 4 * f.H || ld_stats % 4 || ld_dout < f.H * f.C || ld_dout % 4) return HICGAT_EINVAL;
+  if (g.row_end == g.row_begin) return HICGAT_OK;
+  if ((!tiles && (!g.rowptr || !g.col)) || !f.h || !f.a_src || !f.a_dst || !row_stats || !dout || !att_src ||
+      !att_dst || !dh || !da_src)
+    return HICGAT_EINVAL;
+  const SrcArgs a{row_stats, ld_stats, dout, ld_dout / 4, att_src, att_dst, dh, da_src};
+  const bool remap = !(flags & HICGAT_SRC_ROUND_ROBIN);
+  hipStream_t s = (hipStream_t)stream;
+  if (tiles) return agg_bwd_src_tiled(g, f, *tiles, a, s);
+  if (drop) return agg_bwd_src_launch(g, f, a, remap, s, attn_mask_args(*drop));
+  return agg_bwd_src_launch(g, f, a, remap, s);
 }
 
 extern "C" int hicgat_gat_agg_bwd_rows(int N, int H, int C, int row_begin, int row_end, int act,

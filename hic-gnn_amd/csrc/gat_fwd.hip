@@ -82,15 +82,15 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(const int *__restrict__ 
   attn_mask_row<H>(i, rowptr, col, mk, mask);
 }
 
-// The gather half of hicgat_gat_agg_fwd_tiled (gat_tiles.hip): raw sums over the sparse remainder.
-int agg_fwd_split_launch(const int *rowptr, const int *col, const int *rowptr_s, const int *col_s, int row_begin,
-                         int row_end, const float *h, const float *a_src, const float *a_dst, float ns, float *out,
+// The gather half of the forward's tiled form (gat_tiles.hip): raw sums over the sparse remainder.
+int agg_fwd_split_launch(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const hicgat_gat_tiles &t, float *out,
                          float *out2, float *row_stats, hipStream_t s) {
-  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
+  const dim3 grid((g.row_end - g.row_begin + 3) / 4), block(256);
   return with_flags(
       [&](auto train) {
-        hipLaunchKernelGGL((agg_fwd_h2c256_kernel<train.value, 0, true>), grid, block, 0, s, rowptr, col, row_begin,
-                           row_end, h, a_src, a_dst, nullptr, ns, out, out2, row_stats, rowptr_s, col_s);
+        hipLaunchKernelGGL((agg_fwd_h2c256_kernel<train.value, 0, true>), grid, block, 0, s, g.rowptr, g.col,
+                           g.row_begin, g.row_end, f.h, f.a_src, f.a_dst, nullptr, f.neg_slope, out, out2, row_stats,
+                           t.rowptr_s, t.col_s);
         HICGAT_CHECK_LAUNCH();
         return HICGAT_OK;
       },
@@ -106,11 +106,10 @@ constexpr size_t kAggFwdOccLds = 53248;
 
 // The forward's one launch: TRAIN = out2 given, ACT = act, DROP = a mask given.
 template <class... MK>
-int agg_fwd_launch(const int *rowptr, const int *col, int H, int C, int row_begin, int row_end, const float *h,
-                   const float *a_src, const float *a_dst, const float *bias, float ns, int act, float *out,
+int agg_fwd_launch(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const float *bias, int act, float *out,
                    float *out2, float *row_stats, hipStream_t s, MK... mk) {
-  const dim3 grid((row_end - row_begin + 3) / 4), block(256);
-  return for_gat_shape(H, C, [&](auto shape) {
+  const dim3 grid((g.row_end - g.row_begin + 3) / 4), block(256);
+  return for_gat_shape(f.H, f.C, [&](auto shape) {
     return with_flags(
         [&](auto train, auto relu) {
           using S = decltype(shape);
@@ -118,33 +117,17 @@ int agg_fwd_launch(const int *rowptr, const int *col, int H, int C, int row_begi
           constexpr int ACT = relu.value;
           if constexpr (S::h2c256)
             hipLaunchKernelGGL((agg_fwd_h2c256_kernel<TRAIN, ACT, false, MK...>), grid, block,
-                               sizeof...(MK) ? 0 : kAggFwdOccLds, s, rowptr, col, row_begin, row_end, h, a_src, a_dst,
-                               bias, ns, out, out2, row_stats, nullptr, nullptr, mk...);
+                               sizeof...(MK) ? 0 : kAggFwdOccLds, s, g.rowptr, g.col, g.row_begin, g.row_end, f.h,
+                               f.a_src, f.a_dst, bias, f.neg_slope, out, out2, row_stats, nullptr, nullptr, mk...);
           else
-            hipLaunchKernelGGL((agg_fwd_generic_kernel<S::H, S::C, TRAIN, ACT, MK...>), grid, block, 0, s, rowptr,
-                               col, row_begin, row_end, h, a_src, a_dst, bias, ns, out, out2, row_stats, mk...);
+            hipLaunchKernelGGL((agg_fwd_generic_kernel<S::H, S::C, TRAIN, ACT, MK...>), grid, block, 0, s, g.rowptr,
+                               g.col, g.row_begin, g.row_end, f.h, f.a_src, f.a_dst, bias, f.neg_slope, out, out2,
+                               row_stats, mk...);
           HICGAT_CHECK_LAUNCH();
           return HICGAT_OK;
         },
         out2 != nullptr, act != 0);
   });
-}
-
-// What hicgat_gat_agg_fwd and hicgat_gat_agg_drop_fwd check and do; mk: NULL without dropout.
-static int agg_fwd_checked(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C, int row_begin,
-                    int row_end, const float *h, const float *a_src, const float *a_dst, const float *bias,
-                    float neg_slope, int act, float *out, float *out2, float *row_stats, const AttnMaskArgs *mk,
-                    hipStream_t s) {
-  if (N < 0 || nnz < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (act != 0 && act != 1) return HICGAT_EINVAL;
-  if (!gat_shape_supported(H, C)) return HICGAT_EUNSUPPORTED;
-  if (row_end == row_begin) return HICGAT_OK;
-  if (!rowptr || !col || !h || !a_src || !a_dst || !bias || !out || !row_stats) return HICGAT_EINVAL;
-  if (mk)
-    return agg_fwd_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out, out2,
-                          row_stats, s, *mk);
-  return agg_fwd_launch(rowptr, col, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out, out2,
-                        row_stats, s);
 }
 
 }  // namespace hicgat
@@ -163,36 +146,34 @@ extern "C" int hicgat_gat_att_logits(const float *h, const float *att_src, const
   return HICGAT_OK;
 }
 
-extern "C" int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz,
-                                  int H, int C, int row_begin, int row_end, const float *h,
-                                  const float *a_src, const float *a_dst, const float *bias,
-                                  float neg_slope, int act, float *out, float *out2,
-                                  float *row_stats, hicgat_stream_t stream) {
-  return agg_fwd_checked(rowptr, col, N, nnz, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out,
-                         out2, row_stats, nullptr, (hipStream_t)stream);
+// The rules of every form, in the order of include/hicgat.h; the tiled form's own follow in agg_fwd_tiled.
+extern "C" int hicgat_gat_agg_fwd(const hicgat_gat_graph *graph, const hicgat_gat_feats *feats, const float *bias,
+                                  int act, float *out, float *out2, float *row_stats, const hicgat_attn_drop *drop,
+                                  const hicgat_gat_tiles *tiles, hicgat_stream_t stream) {
+  if (!graph || !feats || (drop && tiles)) return HICGAT_EINVAL;
+  if (drop && !attn_drop_ok(*drop)) return HICGAT_EINVAL;
+  const hicgat_gat_graph &g = *graph;
+  const hicgat_gat_feats &f = *feats;
+  if (g.N < 0 || g.nnz < 0 || g.row_begin < 0 || g.row_end > g.N || g.row_begin > g.row_end ||
+      (tiles && tiles->ntiles < 0))
+    return HICGAT_EINVAL;
+  if (act != 0 && act != 1) return HICGAT_EINVAL;
+  if (tiles ? f.H != 2 || f.C != 256 : !gat_shape_supported(f.H, f.C)) return HICGAT_EUNSUPPORTED;
+  if (g.row_end == g.row_begin) return HICGAT_OK;
+  if (!g.rowptr || !g.col || !f.h || !f.a_src || !f.a_dst || !bias || !out || !row_stats) return HICGAT_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (tiles) return agg_fwd_tiled(g, f, *tiles, bias, act, out, out2, row_stats, s);
+  if (drop) return agg_fwd_launch(g, f, bias, act, out, out2, row_stats, s, attn_mask_args(*drop));
+  return agg_fwd_launch(g, f, bias, act, out, out2, row_stats, s);
 }
 
-// ---- attention dropout: hicgat_gat_agg_fwd with each alpha_ij multiplied by its keep factor ------
-extern "C" int hicgat_gat_agg_drop_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
-                                       int row_begin, int row_end, const float *h, const float *a_src,
-                                       const float *a_dst, const float *bias, float neg_slope, int act, float *out,
-                                       float *out2, float *row_stats, double p, uint64_t seed,
-                                       const int64_t *step_counter, int64_t step_value, uint32_t site,
-                                       hicgat_stream_t stream) {
-  if (!p_ok(p) || !attn_site_ok(site) || misaligned(step_counter, 8)) return HICGAT_EINVAL;
-  const AttnMaskArgs mk = attn_mask_args(p, seed, step_counter, step_value, site);
-  return agg_fwd_checked(rowptr, col, N, nnz, H, C, row_begin, row_end, h, a_src, a_dst, bias, neg_slope, act, out,
-                         out2, row_stats, &mk, (hipStream_t)stream);
-}
-
-extern "C" int hicgat_gat_attn_mask(const int32_t *rowptr, const int32_t *col, int N, int H, double p, uint64_t seed,
-                                    const int64_t *step_counter, int64_t step_value, uint32_t site, uint8_t *mask,
-                                    hicgat_stream_t stream) {
-  if (N < 0 || !p_ok(p) || !attn_site_ok(site) || misaligned(step_counter, 8)) return HICGAT_EINVAL;
+extern "C" int hicgat_gat_attn_mask(const int32_t *rowptr, const int32_t *col, int N, int H,
+                                    const hicgat_attn_drop *drop, uint8_t *mask, hicgat_stream_t stream) {
+  if (!drop || N < 0 || !attn_drop_ok(*drop)) return HICGAT_EINVAL;
   if (H < 1 || H > 4) return HICGAT_EUNSUPPORTED;
   if (N == 0) return HICGAT_OK;
   if (!rowptr || !col || !mask) return HICGAT_EINVAL;
-  const AttnMaskArgs mk = attn_mask_args(p, seed, step_counter, step_value, site);
+  const AttnMaskArgs mk = attn_mask_args(*drop);
   const dim3 grid((N + 3) / 4), block(256);
   hipStream_t s = (hipStream_t)stream;
   switch (H) {

@@ -47,14 +47,29 @@ template <bool... B, class F, class... R> int with_flags(F &&f, bool b, R... res
   return b ? with_flags<B..., true>(f, rest...) : with_flags<B..., false>(f, rest...);
 }
 
-// The gather halves of the tiled forms (gat_tiles.hip), defined beside the SPLIT entry kernels:
+// The source pass's operands beside the graph and the features, as hicgat_gat_agg_bwd_src checked them.
+struct SrcArgs {
+  const float *row_stats;
+  int64_t ldr;   // row_stats' row stride in floats
+  const float *dout;
+  int64_t ldq4;  // dout's row stride in float4s
+  const float *att_s, *att_d;
+  float *dh, *da_src;
+};
+
+// The tiled form of each pass (gat_tiles.hip), called by the entry point after the checks every form
+// shares: refuses what only it reads (the tile arrays, splits and the workspace; HICGAT_EINVAL), then
+// launches the gather half and the tile kernels.
+int agg_fwd_tiled(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const hicgat_gat_tiles &t, const float *bias,
+                  int act, float *out, float *out2, float *row_stats, hipStream_t s);
+int agg_bwd_src_tiled(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const hicgat_gat_tiles &t,
+                      const SrcArgs &a, hipStream_t s);
+// Their gather halves, defined beside the SPLIT entry kernels:
 // gat_fwd.hip: raw sums over the sparse remainder
-int agg_fwd_split_launch(const int *rowptr, const int *col, const int *rowptr_s, const int *col_s, int row_begin,
-                         int row_end, const float *h, const float *a_src, const float *a_dst, float ns, float *out,
+int agg_fwd_split_launch(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const hicgat_gat_tiles &t, float *out,
                          float *out2, float *row_stats, hipStream_t s);
 // gat_bwd.hip: the sparse remainder's shares
-int agg_bwd_src_split_launch(const int *rowptr_s, const int *col_s, int row_begin, int row_end, const float *h,
-                             const float *a_src, const float *a_dst, const float *row_stats, int64_t ldr,
-                             const float *dout, int64_t ldq4, float ns, float *dh, float *da_src, hipStream_t s);
+int agg_bwd_src_split_launch(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const hicgat_gat_tiles &t,
+                             const SrcArgs &a, hipStream_t s);
 
 }  // namespace hicgat

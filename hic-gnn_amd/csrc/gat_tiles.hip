@@ -384,93 +384,59 @@ __global__ __launch_bounds__(256) void band_bwd_epilogue(int row_begin, int row_
   if (lane == 0) *reinterpret_cast<float2 *>(da_src + 2 * (size_t)r) = make_float2(ds0, ds1);
 }
 
-}  // namespace hicgat
-
-using namespace hicgat;
-
-static bool tiles_args_ok(const int32_t *tptr, const int32_t *tcol, const uint32_t *tmask, int ntiles) {
-  return tptr && (ntiles == 0 || (tcol && tmask));
+// What only the tiled forms read: the tile arrays, splits (1..64) and the workspace of a split pass.
+static bool tiles_ok(const hicgat_gat_tiles &t, int rows) {
+  if (!t.rowptr_s || !t.col_s || !t.tptr || (t.ntiles != 0 && (!t.tcol || !t.tmask))) return false;
+  if (t.splits < 1 || t.splits > 64) return false;
+  const size_t need = hicgat_gat_tiled_workspace_bytes(rows, t.splits);
+  return need == 0 ||
+         (t.workspace && t.workspace_bytes >= need && (reinterpret_cast<uintptr_t>(t.workspace) & 15) == 0);
 }
+
+int agg_fwd_tiled(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const hicgat_gat_tiles &t, const float *bias,
+                  int act, float *out, float *out2, float *row_stats, hipStream_t s) {
+  const int rows = g.row_end - g.row_begin;
+  if (!tiles_ok(t, rows)) return HICGAT_EINVAL;
+  const int rc = agg_fwd_split_launch(g, f, t, out, out2, row_stats, s);
+  if (rc != HICGAT_OK) return rc;
+  const dim3 grid((rows + 31) / 32, t.splits), block(256), egrid((rows + 3) / 4);
+  float *ws = static_cast<float *>(t.workspace);
+  return with_flags(
+      [&](auto train, auto relu) {
+        constexpr bool TRAIN = train.value;
+        constexpr int ACT = relu.value;
+        hipLaunchKernelGGL((band_fwd_kernel<TRAIN, ACT>), grid, block, 0, s, t.tptr, t.tcol, t.tmask, g.row_begin,
+                           g.row_end, g.N, f.h, f.a_src, f.a_dst, bias, f.neg_slope, out, out2, row_stats, t.splits, ws);
+        if (t.splits > 1)
+          hipLaunchKernelGGL((band_fwd_epilogue<TRAIN, ACT>), egrid, block, 0, s, g.row_begin, g.row_end, t.splits, ws,
+                             bias, out, out2, row_stats);
+        HICGAT_CHECK_LAUNCH();
+        return HICGAT_OK;
+      },
+      out2 != nullptr, act != 0);
+}
+
+int agg_bwd_src_tiled(const hicgat_gat_graph &g, const hicgat_gat_feats &f, const hicgat_gat_tiles &t,
+                      const SrcArgs &a, hipStream_t s) {
+  const int rows = g.row_end - g.row_begin;
+  if (!tiles_ok(t, rows)) return HICGAT_EINVAL;
+  const int rc = agg_bwd_src_split_launch(g, f, t, a, s);
+  if (rc != HICGAT_OK) return rc;
+  float *ws = static_cast<float *>(t.workspace);
+  hipLaunchKernelGGL(band_bwd_kernel, dim3((rows + 31) / 32, t.splits), dim3(256), 0, s, t.tptr, t.tcol, t.tmask,
+                     g.row_begin, g.row_end, g.N, f.h, f.a_src, f.a_dst, a.row_stats, a.ldr, a.dout, a.ldq4, a.att_s,
+                     a.att_d, f.neg_slope, a.dh, a.da_src, t.splits, ws);
+  if (t.splits > 1)
+    hipLaunchKernelGGL(band_bwd_epilogue, dim3((rows + 3) / 4), dim3(256), 0, s, g.row_begin, g.row_end, t.splits, ws,
+                       a.row_stats, a.ldr, a.att_s, a.att_d, a.dh, a.da_src);
+  HICGAT_CHECK_LAUNCH();
+  return HICGAT_OK;
+}
+
+}  // namespace hicgat
 
 extern "C" size_t hicgat_gat_tiled_workspace_bytes(int rows, int splits) {
   if (rows <= 0 || splits <= 1) return 0;
   return (size_t)splits * rows * (2 * 512 + 2) * sizeof(float);
 }
 
-static int tiled_ws_ok(int rows, int splits, const void *workspace, size_t workspace_bytes) {
-  if (splits < 1 || splits > 64) return 0;
-  const size_t need = hicgat_gat_tiled_workspace_bytes(rows, splits);
-  return need == 0 || (workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
-}
-
-extern "C" int hicgat_gat_agg_fwd_tiled(const int32_t *rowptr, const int32_t *col, const int32_t *rowptr_s,
-                                        const int32_t *col_s, const int32_t *tptr, const int32_t *tcol,
-                                        const uint32_t *tmask, int ntiles, int N, int H, int C, int row_begin,
-                                        int row_end, const float *h, const float *a_src, const float *a_dst,
-                                        const float *bias, float neg_slope, int act, float *out, float *out2,
-                                        float *row_stats, int splits, void *workspace, size_t workspace_bytes,
-                                        hicgat_stream_t stream) {
-  if (N < 0 || ntiles < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (act != 0 && act != 1) return HICGAT_EINVAL;
-  if (H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
-  if (row_end == row_begin) return HICGAT_OK;
-  const int rows = row_end - row_begin;
-  if (!rowptr || !col || !rowptr_s || !col_s || !tiles_args_ok(tptr, tcol, tmask, ntiles) || !h || !a_src ||
-      !a_dst || !bias || !out || !row_stats || !tiled_ws_ok(rows, splits, workspace, workspace_bytes))
-    return HICGAT_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  int rc = agg_fwd_split_launch(rowptr, col, rowptr_s, col_s, row_begin, row_end, h, a_src, a_dst, neg_slope, out,
-                                out2, row_stats, s);
-  if (rc != HICGAT_OK) return rc;
-  const dim3 grid((rows + 31) / 32, splits), block(256), egrid((rows + 3) / 4);
-  float *ws = static_cast<float *>(workspace);
-#define HICGAT_BAND_FWD(TR, AC)                                                                                   \
-  do {                                                                                                           \
-    hipLaunchKernelGGL((band_fwd_kernel<TR, AC>), grid, block, 0, s, tptr, tcol, tmask, row_begin, row_end, N, h, \
-                       a_src, a_dst, bias, neg_slope, out, out2, row_stats, splits, ws);                          \
-    if (splits > 1)                                                                                               \
-      hipLaunchKernelGGL((band_fwd_epilogue<TR, AC>), egrid, block, 0, s, row_begin, row_end, splits, ws, bias,   \
-                         out, out2, row_stats);                                                                   \
-  } while (0)
-  if (out2) {
-    if (act) HICGAT_BAND_FWD(true, 1);
-    else HICGAT_BAND_FWD(true, 0);
-  } else {
-    if (act) HICGAT_BAND_FWD(false, 1);
-    else HICGAT_BAND_FWD(false, 0);
-  }
-#undef HICGAT_BAND_FWD
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
-}
-
-extern "C" int hicgat_gat_agg_bwd_src_tiled(const int32_t *rowptr_s, const int32_t *col_s, const int32_t *tptr,
-                                            const int32_t *tcol, const uint32_t *tmask, int ntiles, int N, int H,
-                                            int C, int row_begin, int row_end, const float *h, const float *a_src,
-                                            const float *a_dst, const float *row_stats, int64_t ld_stats,
-                                            const float *dout, int64_t ld_dout, const float *att_src,
-                                            const float *att_dst, float neg_slope, float *dh, float *da_src,
-                                            int splits, void *workspace, size_t workspace_bytes,
-                                            hicgat_stream_t stream) {
-  if (N < 0 || ntiles < 0 || row_begin < 0 || row_end > N || row_begin > row_end) return HICGAT_EINVAL;
-  if (H != 2 || C != 256) return HICGAT_EUNSUPPORTED;
-  if (ld_stats < 4 * H || ld_stats % 4 || ld_dout < H * C || ld_dout % 4) return HICGAT_EINVAL;
-  if (row_end == row_begin) return HICGAT_OK;
-  const int rows = row_end - row_begin;
-  if (!rowptr_s || !col_s || !tiles_args_ok(tptr, tcol, tmask, ntiles) || !h || !a_src || !a_dst || !row_stats ||
-      !dout || !att_src || !att_dst || !dh || !da_src || !tiled_ws_ok(rows, splits, workspace, workspace_bytes))
-    return HICGAT_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  int rc = agg_bwd_src_split_launch(rowptr_s, col_s, row_begin, row_end, h, a_src, a_dst, row_stats, ld_stats, dout,
-                                    ld_dout / 4, neg_slope, dh, da_src, s);
-  if (rc != HICGAT_OK) return rc;
-  float *ws = static_cast<float *>(workspace);
-  hipLaunchKernelGGL(band_bwd_kernel, dim3((rows + 31) / 32, splits), dim3(256), 0, s, tptr, tcol, tmask, row_begin,
-                     row_end, N, h, a_src, a_dst, row_stats, ld_stats, dout, ld_dout / 4, att_src, att_dst, neg_slope,
-                     dh, da_src, splits, ws);
-  if (splits > 1)
-    hipLaunchKernelGGL(band_bwd_epilogue, dim3((rows + 3) / 4), dim3(256), 0, s, row_begin, row_end, splits, ws,
-                       row_stats, ld_stats, att_src, att_dst, dh, da_src);
-  HICGAT_CHECK_LAUNCH();
-  return HICGAT_OK;
-}

@@ -107,14 +107,15 @@ inline uint32_t keep_threshold(double p) {
 
 inline float keep_scale(double p) { return (float)(1.0 / (1.0 - p)); }
 
-// attention dropout: the caller's site must leave kAttnSiteBit free (site < 2^31)
-inline bool attn_site_ok(uint32_t site) { return (site & kAttnSiteBit) == 0; }
+inline bool misaligned(const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; }
 
-inline AttnMaskArgs attn_mask_args(double p, uint64_t seed, const int64_t *step_counter, int64_t step_value,
-                                   uint32_t site) {
-  return AttnMaskArgs{seed, step_counter, step_value, site | kAttnSiteBit, keep_threshold(p), keep_scale(p)};
+// attention dropout: the caller's site must leave kAttnSiteBit free (site < 2^31)
+inline bool attn_drop_ok(const hicgat_attn_drop &d) {
+  return p_ok(d.p) && (d.site & kAttnSiteBit) == 0 && !misaligned(d.step_counter, 8);
 }
 
-inline bool misaligned(const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; }
+inline AttnMaskArgs attn_mask_args(const hicgat_attn_drop &d) {
+  return AttnMaskArgs{d.seed, d.step_counter, d.step_value, d.site | kAttnSiteBit, keep_threshold(d.p), keep_scale(d.p)};
+}
 
 }  // namespace hicgat

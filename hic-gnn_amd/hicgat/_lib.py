@@ -64,9 +64,33 @@ class TailGat(ctypes.Structure):
 
 TAIL_PLAIN, TAIL_HEADS, TAIL_ROWS = 0, 1, 2      # include/hicgat.h HICGAT_TAIL_*
 
+
+class GatGraph(ctypes.Structure):
+    """include/hicgat.h hicgat_gat_graph."""
+    _fields_ = _pointers("rowptr col") + [(n, c_int) for n in "N nnz row_begin row_end".split()]
+
+
+class GatFeats(ctypes.Structure):
+    """include/hicgat.h hicgat_gat_feats."""
+    _fields_ = _pointers("h a_src a_dst") + [("H", c_int), ("C", c_int), ("neg_slope", c_f)]
+
+
+class AttnDrop(ctypes.Structure):
+    """include/hicgat.h hicgat_attn_drop."""
+    _fields_ = [("p", c_d), ("seed", c_u64), ("step_counter", c_p), ("step_value", c_i64), ("site", c_u32)]
+
+
+class GatTiles(ctypes.Structure):
+    """include/hicgat.h hicgat_gat_tiles."""
+    _fields_ = _pointers("rowptr_s col_s tptr tcol tmask") + [("ntiles", c_int), ("splits", c_int),
+                                                              ("workspace", c_p), ("workspace_bytes", c_sz)]
+
+
 c_wjobs, c_cjobs, c_gjobs = ctypes.POINTER(WgradJob), ctypes.POINTER(ColsumJob), ctypes.POINTER(GemmJob)
 c_tailw, c_taila, c_tailg, c_tailgat = (ctypes.POINTER(TailWeights), ctypes.POINTER(TailActs),
                                         ctypes.POINTER(TailGrads), ctypes.POINTER(TailGat))
+c_graph, c_feats, c_drop, c_tiles = (ctypes.POINTER(GatGraph), ctypes.POINTER(GatFeats), ctypes.POINTER(AttnDrop),
+                                     ctypes.POINTER(GatTiles))
 
 # name -> (restype, argtypes); mirrors include/hicgat.h one to one
 SIGNATURES = {
@@ -78,26 +102,14 @@ SIGNATURES = {
     "hicgat_cont2dist_workspace_bytes": (c_sz, [c_int]),
     "hicgat_gat_linear_att": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
     "hicgat_gat_att_logits": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
-    "hicgat_gat_agg_fwd": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p,
-                                   c_p, c_f, c_int, c_p, c_p, c_p, c_p]),
+    "hicgat_gat_agg_fwd": (c_int, [c_graph, c_feats, c_p, c_int, c_p, c_p, c_p, c_drop, c_tiles, c_p]),
     "hicgat_gat_agg_bwd_dst": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
                                        c_f, c_p, c_p]),
     "hicgat_gat_agg_bwd_rows": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p,
                                         c_i64, c_p, c_p]),
-    "hicgat_gat_agg_bwd_src": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
-                                       c_i64, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_int, c_p]),
-    "hicgat_gat_agg_drop_fwd": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p,
-                                        c_p, c_f, c_int, c_p, c_p, c_p, c_d, c_u64, c_p, c_i64, c_u32, c_p]),
-    "hicgat_gat_agg_drop_bwd_src": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
-                                            c_i64, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_int, c_d, c_u64, c_p,
-                                            c_i64, c_u32, c_p]),
-    "hicgat_gat_attn_mask": (c_int, [c_p, c_p, c_int, c_int, c_d, c_u64, c_p, c_i64, c_u32, c_p, c_p]),
-    "hicgat_gat_agg_fwd_tiled": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int,
-                                         c_int, c_p, c_p, c_p, c_p, c_f, c_int, c_p, c_p, c_p, c_int, c_p, c_sz,
-                                         c_p]),
-    "hicgat_gat_agg_bwd_src_tiled": (c_int, [c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                             c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_f, c_p, c_p, c_int,
-                                             c_p, c_sz, c_p]),
+    "hicgat_gat_agg_bwd_src": (c_int, [c_graph, c_feats, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_int, c_drop,
+                                       c_tiles, c_p]),
+    "hicgat_gat_attn_mask": (c_int, [c_p, c_p, c_int, c_int, c_drop, c_p, c_p]),
     "hicgat_gat_tiled_workspace_bytes": (c_sz, [c_int, c_int]),
     "hicgat_gat_param_grad": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_int, c_p,
                                       c_sz, c_p]),

@@ -238,7 +238,7 @@ TILE_SPLITS = int(os.environ.get("HICGAT_TILE_SPLITS", "0"))   # 0 = from the ro
 
 
 class Tiles:
-    """Dense-tile split of rows [r0, r1) of a CSR (include/hicgat.h, hicgat_gat_agg_fwd_tiled):
+    """Dense-tile split of rows [r0, r1) of a CSR (include/hicgat.h, hicgat_gat_tiles):
     ``tptr`` [nrb+1] / ``tcol`` [ntiles] / ``tmask`` [ntiles*32] (int32 bit patterns of uint32
     words) for the row blocks' dense 32x32 tiles, ``rowptr_s`` / ``col_s`` the CSR of every other
     edge; ``n_dense`` edges are in tiles."""

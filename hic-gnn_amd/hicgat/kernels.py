@@ -51,6 +51,17 @@ def _operands(cls, tensors, **scalars):
     return cls(**{k: None if t is None else t.data_ptr() for k, t in tensors.items()}, **scalars)
 
 
+def _attn_drop(drop):
+    """Attention dropout (include/hicgat.h hicgat_attn_drop; None: NULL) from ``drop`` = (p, seed, step_ctr,
+    step_value, site): the step comes from the device count ``step_ctr`` (int64 [1]) or, if that is None, from
+    ``step_value``."""
+    if drop is None:
+        return None
+    p, seed, step_ctr, step_value, site = drop
+    return _operands(_lib.AttnDrop, dict(step_counter=step_ctr), p=float(p), seed=int(seed),
+                     step_value=int(step_value), site=int(site))
+
+
 # K-split of a node-row GEMM that would leave the chip mostly idle (a rank's shard of the multi-GPU
 # step): the library's rule, hicgat_gemm_row_splits (gemm.hip).  HICGAT_ROW_SPLIT=0: off (A/B).
 ROW_SPLIT = os.environ.get("HICGAT_ROW_SPLIT", "1") != "0"
@@ -106,47 +117,37 @@ class HipKernels:
     def agg_fwd(self, rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, out, row_stats):
         self.agg_fwd_act(rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, 0, out, None, row_stats)
 
-    def agg_fwd_act(self, rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, act, out, out2, row_stats):
-        """Training form: ``act`` 1 = relu epilogue; ``out2`` (or None) = sum alpha lrelu' h."""
-        N = h.shape[0]
+    def _gat_operands(self, rowptr, col, r0, r1, h, a_src, a_dst, ns, drop, tiles):
+        """The four operand structs of the two gathering passes (include/hicgat.h; ``drop`` / ``tiles`` None: NULL).
+        With ``tiles`` the rows are [tiles.r0, tiles.r1), and a range that is passed must be that one."""
         H = a_src.shape[1]
-        C = h.shape[1] // H
-        with _timed("gat_agg_fwd"):
-            _lib.check(self.lib.hicgat_gat_agg_fwd(P(rowptr), P(col), N, col.numel(), H, C, r0, r1, P(h), P(a_src),
-                                                   P(a_dst), P(bias), float(ns), int(act), P(out), P(out2),
-                                                   P(row_stats), _lib.stream(h.device)), "hicgat_gat_agg_fwd")
-
-    def agg_fwd_tiled(self, rowptr, col, tiles, h, a_src, a_dst, bias, ns, act, out, out2, row_stats):
-        """``agg_fwd_act`` over rows [tiles.r0, tiles.r1) with the dense tiles on the matrix cores."""
-        N = h.shape[0]
-        H = a_src.shape[1]
-        C = h.shape[1] // H
         t = tiles
-        ws = self.tiled_workspace(t, h.device)
-        with _timed("gat_agg_fwd"):
-            _lib.check(self.lib.hicgat_gat_agg_fwd_tiled(
-                P(rowptr), P(col), P(t.rowptr_s), P(t.col_s), P(t.tptr), P(t.tcol), P(t.tmask), t.ntiles, N, H, C,
-                t.r0, t.r1, P(h), P(a_src), P(a_dst), P(bias), float(ns), int(act), P(out), P(out2), P(row_stats),
-                t.splits, P(ws), 0 if ws is None else ws.numel(), _lib.stream(h.device)), "hicgat_gat_agg_fwd_tiled")
+        if t is not None:
+            assert (r0 is None or r0 == t.r0) and (r1 is None or r1 == t.r1)
+            r0, r1 = t.r0, t.r1
+            ws = self.tiled_workspace(t, h.device)
+            t = _operands(_lib.GatTiles, dict(rowptr_s=t.rowptr_s, col_s=t.col_s, tptr=t.tptr, tcol=t.tcol,
+                                              tmask=t.tmask, workspace=ws), ntiles=t.ntiles, splits=t.splits,
+                          workspace_bytes=0 if ws is None else ws.numel())
+            t.ws = ws   # lives until the caller has launched
+        graph = _operands(_lib.GatGraph, dict(rowptr=rowptr, col=col), N=h.shape[0],
+                          nnz=0 if col is None else col.numel(), row_begin=r0, row_end=r1)
+        feats = _operands(_lib.GatFeats, dict(h=h, a_src=a_src, a_dst=a_dst), H=H, C=h.shape[1] // H,
+                          neg_slope=float(ns))
+        return graph, feats, _attn_drop(drop), t
+
+    def agg_fwd_act(self, rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, act, out, out2, row_stats, drop=None,
+                    tiles=None):
+        """Training form: ``act`` 1 = relu epilogue; ``out2`` (or None) = sum alpha lrelu' h.  ``drop``: every
+        alpha multiplied by its keep factor (out, out2; not S3); ``tiles``: the dense tiles on the matrix cores."""
+        graph, feats, d, t = self._gat_operands(rowptr, col, r0, r1, h, a_src, a_dst, ns, drop, tiles)
+        with _timed("gat_agg_drop_fwd" if drop is not None else "gat_agg_fwd"):
+            _lib.check(self.lib.hicgat_gat_agg_fwd(graph, feats, P(bias), int(act), P(out), P(out2), P(row_stats), d, t,
+                                                   _lib.stream(h.device)), "hicgat_gat_agg_fwd")
 
     def tiled_workspace(self, t, device):
         nb = self.lib.hicgat_gat_tiled_workspace_bytes(t.r1 - t.r0, t.splits)
         return _lib.workspace(nb, device) if nb else None
-
-    def agg_bwd_src_tiled(self, tiles, h, a_src, a_dst, row_stats, dout, att_l, att_r, ns, dh, da_src):
-        """``agg_bwd_src`` over rows [tiles.r0, tiles.r1) with the dense tiles on the matrix cores."""
-        N = h.shape[0]
-        H = a_src.shape[1]
-        C = h.shape[1] // H
-        assert row_stats.stride(1) == 1 and dout.stride(1) == 1
-        t = tiles
-        ws = self.tiled_workspace(t, h.device)
-        with _timed("gat_agg_bwd_src"):
-            _lib.check(self.lib.hicgat_gat_agg_bwd_src_tiled(
-                P(t.rowptr_s), P(t.col_s), P(t.tptr), P(t.tcol), P(t.tmask), t.ntiles, N, H, C, t.r0, t.r1, P(h),
-                P(a_src), P(a_dst), P(row_stats), row_stats.stride(0), P(dout), dout.stride(0), P(att_l), P(att_r),
-                float(ns), P(dh), P(da_src), t.splits, P(ws), 0 if ws is None else ws.numel(),
-                _lib.stream(h.device)), "hicgat_gat_agg_bwd_src_tiled")
 
     def agg_bwd_rows(self, r0, r1, act, g, y, bias, out2, dout, row_stats):
         """Destination half of the backward without a gather (after ``agg_fwd_act`` with out2);
@@ -172,59 +173,24 @@ class HipKernels:
     SRC_ROUND_ROBIN = 1   # include/hicgat.h HICGAT_SRC_ROUND_ROBIN
 
     def agg_bwd_src(self, rowptr, col, r0, r1, h, a_src, a_dst, row_stats, dout, att_l, att_r, ns, dh, da_src,
-                    round_robin=False):
-        """``round_robin``: row blocks spread over the XCDs (the multi-GPU slab pass, hicgat.dist)."""
-        N = h.shape[0]
-        H = a_src.shape[1]
-        C = h.shape[1] // H
+                    round_robin=False, drop=None, tiles=None):
+        """``round_robin``: row blocks spread over the XCDs (the multi-GPU slab pass, hicgat.dist).  ``drop``: the
+        forward's keep factors recomputed from (col[e], r); ``tiles``: the dense tiles on the matrix cores (the
+        remainder's CSR is read, ``rowptr`` / ``col`` are not and may be None)."""
+        graph, feats, d, t = self._gat_operands(rowptr, col, r0, r1, h, a_src, a_dst, ns, drop, tiles)
         # row_stats / dout may be row-strided views (the packed all-gather buffer of hicgat.dist)
         assert row_stats.stride(1) == 1 and dout.stride(1) == 1
-        with _timed("gat_agg_bwd_src"):
-            _lib.check(self.lib.hicgat_gat_agg_bwd_src(P(rowptr), P(col), N, H, C, r0, r1, P(h), P(a_src),
-                                                       P(a_dst), P(row_stats), row_stats.stride(0), P(dout),
-                                                       dout.stride(0), P(att_l), P(att_r), float(ns), P(dh),
-                                                       P(da_src), self.SRC_ROUND_ROBIN if round_robin else 0,
-                                                       _lib.stream(h.device)),
-                       "hicgat_gat_agg_bwd_src")
-
-    # -- attention dropout (include/hicgat.h "attention dropout"): the DROP forms of the two gathers --
-    # ``drop`` = (p, seed, step_ctr, step_value, site): the step comes from the device count
-    # ``step_ctr`` (int64 [1]) or, if that is None, from ``step_value``
-    def agg_drop_fwd(self, rowptr, col, r0, r1, h, a_src, a_dst, bias, ns, act, out, out2, row_stats, drop):
-        """``agg_fwd_act`` with every alpha multiplied by its keep factor (out, out2; not S3)."""
-        N = h.shape[0]
-        H = a_src.shape[1]
-        C = h.shape[1] // H
-        p, seed, step_ctr, step_value, site = drop
-        with _timed("gat_agg_drop_fwd"):
-            _lib.check(self.lib.hicgat_gat_agg_drop_fwd(P(rowptr), P(col), N, col.numel(), H, C, r0, r1, P(h),
-                                                        P(a_src), P(a_dst), P(bias), float(ns), int(act), P(out),
-                                                        P(out2), P(row_stats), float(p), int(seed), P(step_ctr),
-                                                        int(step_value), int(site), _lib.stream(h.device)),
-                       "hicgat_gat_agg_drop_fwd")
-
-    def agg_drop_bwd_src(self, rowptr, col, r0, r1, h, a_src, a_dst, row_stats, dout, att_l, att_r, ns, dh, da_src,
-                         drop, round_robin=False):
-        """``agg_bwd_src`` with the forward's keep factors recomputed from (col[e], r)."""
-        N = h.shape[0]
-        H = a_src.shape[1]
-        C = h.shape[1] // H
-        assert row_stats.stride(1) == 1 and dout.stride(1) == 1
-        p, seed, step_ctr, step_value, site = drop
-        with _timed("gat_agg_drop_bwd_src"):
-            _lib.check(self.lib.hicgat_gat_agg_drop_bwd_src(
-                P(rowptr), P(col), N, H, C, r0, r1, P(h), P(a_src), P(a_dst), P(row_stats), row_stats.stride(0),
-                P(dout), dout.stride(0), P(att_l), P(att_r), float(ns), P(dh), P(da_src),
-                self.SRC_ROUND_ROBIN if round_robin else 0, float(p), int(seed), P(step_ctr), int(step_value),
-                int(site), _lib.stream(h.device)), "hicgat_gat_agg_drop_bwd_src")
+        with _timed("gat_agg_drop_bwd_src" if drop is not None else "gat_agg_bwd_src"):
+            _lib.check(self.lib.hicgat_gat_agg_bwd_src(graph, feats, P(row_stats), row_stats.stride(0), P(dout),
+                                                       dout.stride(0), P(att_l), P(att_r), P(dh), P(da_src),
+                                                       self.SRC_ROUND_ROBIN if round_robin else 0, d, t,
+                                                       _lib.stream(h.device)), "hicgat_gat_agg_bwd_src")
 
     def attn_mask(self, rowptr, col, H, mask, drop):
         """The keep bits of every (edge, head) into ``mask`` (contiguous uint8 [nnz, H])."""
         assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape == (col.numel(), H)
-        p, seed, step_ctr, step_value, site = drop
-        _lib.check(self.lib.hicgat_gat_attn_mask(P(rowptr), P(col), rowptr.numel() - 1, int(H), float(p), int(seed),
-                                                 P(step_ctr), int(step_value), int(site), P(mask),
-                                                 _lib.stream(mask.device)), "hicgat_gat_attn_mask")
+        _lib.check(self.lib.hicgat_gat_attn_mask(P(rowptr), P(col), rowptr.numel() - 1, int(H), _attn_drop(drop),
+                                                 P(mask), _lib.stream(mask.device)), "hicgat_gat_attn_mask")
         return mask
 
     def param_grad(self, h, dout, da_src, row_stats, H, out=None, accumulate=False):

@@ -54,7 +54,7 @@ class _GATConvFn(torch.autograd.Function):
     def forward(ctx, x, W, att_l, att_r, bias, rowptr, col, negative_slope, act, tiles=None, tmap=None, drop=None):
         # tmap: only from _GATConvAttnFn / _GATConvDropFn, which run this body and then add the attention
         # weights; drop: only from _GATConvDropFn, the (p, seed, step_ctr, step_value, site) of
-        # kernels.agg_drop_fwd -- attention dropout in the two gathers (never with tiles)
+        # kernels.agg_fwd_act -- attention dropout in the two gathers (never with tiles)
         _lib.lib()
         _dev_check(x, W, att_l, att_r, bias, rowptr, col)
         K = kernels.default()
@@ -71,12 +71,8 @@ class _GATConvFn(torch.autograd.Function):
         row_stats = torch.empty((N, 4 * H), dtype=torch.float32, device=x.device)
         train = any(ctx.needs_input_grad[:5])
         out2 = torch.empty((N, D), dtype=torch.float32, device=x.device) if train else None
-        if drop is not None:
-            K.agg_drop_fwd(rowptr, col, 0, N, h, a_src, a_dst, b, negative_slope, act, out, out2, row_stats, drop)
-        elif tiles is not None:
-            K.agg_fwd_tiled(rowptr, col, tiles, h, a_src, a_dst, b, negative_slope, act, out, out2, row_stats)
-        else:
-            K.agg_fwd_act(rowptr, col, 0, N, h, a_src, a_dst, b, negative_slope, act, out, out2, row_stats)
+        K.agg_fwd_act(rowptr, col, 0, N, h, a_src, a_dst, b, negative_slope, act, out, out2, row_stats, drop=drop,
+                      tiles=tiles)
         ctx.tiles = tiles
         ctx.drop = drop
         ctx.rows_state = None
@@ -129,16 +125,12 @@ class _GATConvFn(torch.autograd.Function):
         pW, pl, pr, pb = ctx.params
         sinks = (_sink(pl), _sink(pr), _sink(pb) if ctx.has_bias else None)
         use_sinks = all(t is not None for t in sinks)
-        if ctx.drop is not None:
+        stamped = ctx.tiles is None   # the untiled pass alone
+        if stamped:
             streams.stamp("src_begin")
-            K.agg_drop_bwd_src(rowptr, col, 0, N, h, a_src, a_dst, row_stats, dout, al, ar, ctx.ns, dh, da_src,
-                               ctx.drop)
-            streams.stamp("src_end")
-        elif ctx.tiles is not None:
-            K.agg_bwd_src_tiled(ctx.tiles, h, a_src, a_dst, row_stats, dout, al, ar, ctx.ns, dh, da_src)
-        else:
-            streams.stamp("src_begin")
-            K.agg_bwd_src(rowptr, col, 0, N, h, a_src, a_dst, row_stats, dout, al, ar, ctx.ns, dh, da_src)
+        K.agg_bwd_src(rowptr, col, 0, N, h, a_src, a_dst, row_stats, dout, al, ar, ctx.ns, dh, da_src, drop=ctx.drop,
+                      tiles=ctx.tiles)
+        if stamped:
             streams.stamp("src_end")
         side_flush(after=fork)
         if G is not None:

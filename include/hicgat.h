@@ -77,27 +77,96 @@ int hicgat_gat_att_logits(const float *h, const float *att_src, const float *att
  *   e_ij = leaky_relu(a_src[j] + a_dst[i], neg_slope)
  *   alpha_ij = exp(e_ij - max_i) / (sum_i + 1e-16)        (torch_geometric.utils.softmax, ptr path)
  *   out[i] = sum_j alpha_ij * h[j] + bias                  (segment_csr sum; concat=True)
- * Only rows [row_begin, row_end) are computed (a rank's destination shard; 0..N on one GPU);
- * every per-row array is indexed by the GLOBAL row id: h, a_src, a_dst [N, .] (the neighbour
- * rows of the shard must be present), out [N, H*C] (rows of the range written),
- * row_stats [N, 4H] = (max[H], sum[H], delta[H], da_dst[H]) -- max/sum written here, delta/da_dst
- * by hicgat_gat_agg_bwd_dst.  Supported: C % 128 == 0, H*C a multiple of 256, H*C <= 1024, H <= 4
+ * The operands that the forward and the source pass of the backward (hicgat_gat_agg_bwd_src) share
+ * come in four structs; the last two select the form of the pass and are NULL for the plain gather.
+ * hicgat_gat_graph: rowptr [N + 1] / col [nnz] and the destination rows [row_begin, row_end) of the
+ *   pass (a rank's shard; 0..N on one GPU).  nnz = rowptr[N] (checked >= 0 only, by the forward only).
+ * hicgat_gat_feats: h [N, H*C] (lin_l's output), a_src / a_dst [N, H], neg_slope.  Every per-row array
+ *   of a pass is indexed by the GLOBAL row id (the neighbour rows of the shard must be present).
+ * hicgat_attn_drop: PyG 1.7.2 GATConv(dropout=p), `alpha = F.dropout(alpha, p, training)` in message(),
+ *   inside the two gathering passes.  Every alpha_ij of the forward is multiplied, per head, by m_ij in
+ *   {0, scale}; the softmax itself (row_stats max / sum, hicgat_gat_alpha) is that of the undropped
+ *   row, and self loops are dropped like any other edge.  The mask is a pure function of (seed, step,
+ *   site, destination row i, source row j, head), with i and j GLOBAL node ids, so it depends neither
+ *   on the launch geometry, nor on the row range, nor on the edge's position -- the source pass
+ *   recomputes the bits of edge (i -> r) from (col[e], r) and no [nnz, H] tensor exists.
+ *   Philox4x32-10 as under "feature dropout" below:
+ *     counter = (i, j, step & 0xffffffff, site | HICGAT_ATTN_SITE_BIT);  key = (seed & 0xffffffff, seed >> 32);
+ *     head hh uses output word r[hh] (H <= 4: one call per edge);  kept iff r[hh] >= T,
+ *     T = min(floor(p * 2^32), 2^32 - 1);  m = kept ? scale : 0,  scale = (float)(1.0 / (1.0 - p)).
+ *   HICGAT_ATTN_SITE_BIT keeps these sites apart from the feature-dropout sites that share a seed and a
+ *   step count; the caller's site must be < 2^31.  step = *step_counter when the pointer is given (a
+ *   device int64, 8-B aligned; NULL-able), else step_value.  p = 0 keeps everything (scale 1).  p
+ *   outside [0, 1) or NaN, site >= 2^31, a misaligned step_counter: HICGAT_EINVAL, before the shape is
+ *   looked at.  A gradient that arrives through alpha itself (hicgat_gat_alpha_bwd_*) sees no mask:
+ *   PyG returns the pre-dropout alpha.  The dense-tile, aggregate-first (hicgat_xagg_*) and stand-alone
+ *   destination (hicgat_gat_agg_bwd_dst) forms have no dropout: drop together with tiles is HICGAT_EINVAL.
+ * hicgat_gat_tiles: the dense-tile form (gat_tiles.hip; formerly hicgat_gat_agg_fwd_tiled and its
+ *   source-pass twin), the same results (fp32; the tiles' sums are added in another order) with the dense part of the graph on
+ *   the matrix cores, H == 2 and C == 256 only (else HICGAT_EUNSUPPORTED).  The edge set is split in two:
+ *     tiles: rows [row_begin, row_end) in blocks of 32 (block b = rows row_begin + 32b ..);
+ *       tptr [nrb + 1] (nrb = ceil((row_end - row_begin) / 32)) indexes tcol [ntiles] (a 32-column
+ *       block: columns 32*tcol[t] ..) and tmask [ntiles * 32] (bit c of word 32t + i: the edge
+ *       (row_begin + 32b + i, 32*tcol[t] + c) exists); tiles of a block in any order, each edge in at
+ *       most one tile;
+ *     rowptr_s / col_s: the CSR (N + 1 row pointers, rows of the range) of every OTHER edge.
+ *   The graph's rowptr / col (the whole rows) give the forward its softmax statistics; the source pass
+ *   reads only rowptr_s / col_s, and the graph's two may be NULL there.  The tiles' products run as
+ *   dense 32 x 32 x 32 x 512 blocks on v_mfma_f32_32x32x2_f32 (weights 0 off the edge set).  Built
+ *   from the CSR by hicgat.graph.build_tiles (a 32x32 tile is dense when it holds >= min_edges edges).
+ *   splits (1..64): the tiles of a row block are spread over `splits` workgroups (a graph with few row
+ *   blocks, e.g. a dense 2000-node map: 63); splits > 1 needs a 16-B aligned workspace of
+ *   hicgat_gat_tiled_workspace_bytes(row_end - row_begin, splits) bytes for the partial sums, which
+ *   one more pass adds in split order. */
+typedef struct {
+  const int32_t *rowptr, *col;
+  int N, nnz, row_begin, row_end;
+} hicgat_gat_graph;
+typedef struct {
+  const float *h, *a_src, *a_dst;
+  int H, C;
+  float neg_slope;
+} hicgat_gat_feats;
+#define HICGAT_ATTN_SITE_BIT 0x80000000u
+enum { HICGAT_ATTN_SITE_MAX = 0x7fffffff };   /* the largest site a caller may pass */
+typedef struct {
+  double p;
+  uint64_t seed;
+  const int64_t *step_counter;
+  int64_t step_value;
+  uint32_t site;
+} hicgat_attn_drop;
+typedef struct {
+  const int32_t *rowptr_s, *col_s, *tptr, *tcol;
+  const uint32_t *tmask;
+  int ntiles, splits;
+  void *workspace;
+  size_t workspace_bytes;
+} hicgat_gat_tiles;
+size_t hicgat_gat_tiled_workspace_bytes(int rows, int splits);
+/* The forward: out [N, H*C] (rows of the range written) and row_stats [N, 4H] = (max[H], sum[H],
+ * delta[H], da_dst[H]) -- max/sum written here, delta/da_dst by the backward's destination pass.
+ * Supported: C % 128 == 0, H*C a multiple of 256, H*C <= 1024, H <= 4
  * (every GATConv of models.py: (H, C) = (1, 256), (1, 512), (2, 128), (2, 256), (2, 512), (4, 256), ...);
  * other shapes return HICGAT_EUNSUPPORTED.  H == 2, C == 256 (the flagship's GATConv(512, 256,
  * heads=2), models.py:619) has entry kernels and launch parameters of its own around the per-row bodies
  * that every shape shares (gat_agg.hpp); one dispatcher (gat_launch.hpp) launches both kinds.
  * The same set holds for hicgat_gat_agg_bwd_dst, hicgat_gat_agg_bwd_rows and hicgat_gat_agg_bwd_src;
- * the tiled (hicgat_gat_agg_*_tiled) and aggregate-first (hicgat_xagg_*) forms stay H == 2, C == 256.
- * nnz = rowptr[N] (checked >= 0 only).  bias [H*C].  act = 1 writes out = relu(sum + bias) (the relu
- * that follows the GATConv at models.py:637), act = 0 the plain sum + bias (inference: act = 0,
- * out2 = NULL).  out2 != NULL (training) also writes, from the same gathered rows, out2 [N, H*C] =
+ * the aggregate-first (hicgat_xagg_*) forms stay H == 2, C == 256.
+ * bias [H*C].  act = 1 writes out = relu(sum + bias) (the relu that follows the GATConv at
+ * models.py:637), act = 0 the plain sum + bias (inference: act = 0, out2 = NULL); any other act:
+ * HICGAT_EINVAL.  out2 != NULL (training) also writes, from the same gathered rows, out2 [N, H*C] =
  * sum_j alpha_ij lrelu'(e_ij) h_j and S3[i,h] = sum_j alpha_ij lrelu'(e_ij) into row_stats[i, 2H..3H)
  * -- the inputs that let hicgat_gat_agg_bwd_rows form the destination half of the backward without a
- * gather.  No other pointer may be NULL. */
-int hicgat_gat_agg_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
-                       int row_begin, int row_end, const float *h, const float *a_src,
-                       const float *a_dst, const float *bias, float neg_slope, int act,
-                       float *out, float *out2, float *row_stats, hicgat_stream_t stream);
+ * gather.  No pointer but out2, drop and tiles may be NULL (graph and feats neither: HICGAT_EINVAL); an
+ * empty row range is a no-op that looks at no pointer inside or beside the structs.
+ *   drop: out[i] = sum_j alpha_ij m_ij h[j] + bias (then relu, act = 1), out2[i] =
+ *     sum_j alpha_ij lrelu'(e_ij) m_ij h[j] (masked) and S3[i] = sum_j alpha_ij lrelu'(e_ij) (NOT masked).
+ *   tiles: the gather computes each row's statistics over ALL its edges and the sums of the remainder;
+ *     the tile kernel adds the tiles' products and applies bias / relu.  S3 as without tiles. */
+int hicgat_gat_agg_fwd(const hicgat_gat_graph *graph, const hicgat_gat_feats *feats, const float *bias, int act,
+                       float *out, float *out2, float *row_stats, const hicgat_attn_drop *drop,
+                       const hicgat_gat_tiles *tiles, hicgat_stream_t stream);
 
 /* ---- a10 (part): backward of a4+a5 ----------------------------------------------------------
  * Pass 1 (destination side, rows of the range):  g_ij = <dout[i,h,:], h[j,h,:]>,
@@ -123,63 +192,30 @@ int hicgat_gat_agg_bwd_rows(int N, int H, int C, int row_begin, int row_end, int
                             int64_t ld_dout, float *row_stats, hicgat_stream_t stream);
 /* Pass 2 (above): dh [N, H*C] and da_src [N, H], rows of the range written.  Row i of dout is at
  * dout + i*ld_dout and of row_stats at row_stats + i*ld_stats (floats; ld_dout >= H*C, ld_stats >= 4H,
- * both multiples of 4): contiguous tensors pass H*C and 4H, hicgat.dist one all-gathered
- * [dout | row stats] buffer per row.  att_src / att_dst [H, C].  No pointer may be NULL.  flags: 0, or
- * HICGAT_SRC_ROUND_ROBIN, which spreads consecutive row blocks over the XCDs instead of giving each
- * XCD a contiguous row range (the multi-GPU "slab" pass, hicgat.dist, whose heavy rows are one
- * contiguous block); any other bit: HICGAT_EINVAL. */
-enum { HICGAT_SRC_ROUND_ROBIN = 1 };
-int hicgat_gat_agg_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H, int C, int row_begin,
-                           int row_end, const float *h, const float *a_src, const float *a_dst,
-                           const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
-                           const float *att_src, const float *att_dst, float neg_slope, float *dh, float *da_src,
-                           int flags, hicgat_stream_t stream);
-/* ---- attention dropout: PyG 1.7.2 GATConv(dropout=p), `alpha = F.dropout(alpha, p, training)` in
- * message(), inside the two gathering passes -------------------------------------------------------
- * Every alpha_ij of the forward is multiplied, per head, by m_ij in {0, scale}; the softmax itself
- * (row_stats max / sum, hicgat_gat_alpha) is that of the undropped row, and self loops are dropped
- * like any other edge.  The mask is a pure function of (seed, step, site, destination row i, source
- * row j, head), with i and j GLOBAL node ids, so it depends neither on the launch geometry, nor on
- * the row range, nor on the edge's position -- the source pass recomputes the bits of edge (i -> r)
- * from (col[e], r) and no [nnz, H] tensor exists.  Philox4x32-10 as under "feature dropout" below:
- *   counter = (i, j, step & 0xffffffff, site | HICGAT_ATTN_SITE_BIT);  key = (seed & 0xffffffff, seed >> 32);
- *   head hh uses output word r[hh] (H <= 4: one call per edge);  kept iff r[hh] >= T,
- *   T = min(floor(p * 2^32), 2^32 - 1);  m = kept ? scale : 0,  scale = (float)(1.0 / (1.0 - p)).
- * HICGAT_ATTN_SITE_BIT keeps these sites apart from the feature-dropout sites that share a seed and a
- * step count; the caller's site must be < 2^31.  step = *step_counter when the pointer is given (a
- * device int64, 8-B aligned; NULL-able), else step_value.
- *   hicgat_gat_agg_drop_fwd: hicgat_gat_agg_fwd with  out[i] = sum_j alpha_ij m_ij h[j] + bias  (then
- *     relu, act = 1),  out2[i] = sum_j alpha_ij lrelu'(e_ij) m_ij h[j]  (masked) and
- *     S3[i] = sum_j alpha_ij lrelu'(e_ij)  (NOT masked).  out2 NULL-able as there.
- *   hicgat_gat_agg_bwd_rows is unchanged: delta_i = <dout_i, out_i - bias> = sum_k alpha_ik m_ik g_ik and
- *     da_dst_i = <dout_i, out2_i> - delta_i S3_i are the dropped layer's.
- *   hicgat_gat_agg_drop_bwd_src: hicgat_gat_agg_bwd_src with
+ * both multiples of 4, else HICGAT_EINVAL): contiguous tensors pass H*C and 4H, hicgat.dist one
+ * all-gathered [dout | row stats] buffer per row.  att_src / att_dst [H, C].  graph, feats, drop and
+ * tiles as for the forward; no other pointer may be NULL.  flags: 0, or HICGAT_SRC_ROUND_ROBIN, which
+ * spreads consecutive row blocks over the XCDs instead of giving each XCD a contiguous row range (the
+ * multi-GPU "slab" pass, hicgat.dist, whose heavy rows are one contiguous block); any other bit, or the
+ * flag together with tiles: HICGAT_EINVAL.
+ *   drop: the forward's keep factors recomputed,
  *     dh[r] = sum_i alpha_ir m_ir dout[i] + da_src[r] (x) att_l + da_dst[r] (x) att_r,
  *     da_src[r] = <sum_i alpha_ir s_ir m_ir dout_i, h_r> - sum_i alpha_ir s_ir delta_i   (s = lrelu').
- *   hicgat_gat_attn_mask: mask[e * H + hh] = kept ? 1 : 0 (uint8 [nnz, H], self-looped CSR order) from
- *     the same device function (tests, tools); 1 <= H <= 4, else HICGAT_EUNSUPPORTED.
- * A gradient that arrives through alpha itself (hicgat_gat_alpha_bwd_*) sees no mask: PyG returns the
- * pre-dropout alpha.  Checked before any launch: p outside [0, 1) or NaN, site >= 2^31, a misaligned
- * step_counter and everything hicgat_gat_agg_fwd / _bwd_src refuse -> HICGAT_EINVAL; an unsupported
- * (H, C) -> HICGAT_EUNSUPPORTED; an empty row range (N == 0 for the mask) is a no-op.  p = 0 keeps
- * everything (scale 1).  The tiled (hicgat_gat_agg_*_tiled), aggregate-first (hicgat_xagg_*) and
- * stand-alone destination (hicgat_gat_agg_bwd_dst) forms have no dropout. */
-#define HICGAT_ATTN_SITE_BIT 0x80000000u
-enum { HICGAT_ATTN_SITE_MAX = 0x7fffffff };   /* the largest site a caller may pass */
-int hicgat_gat_agg_drop_fwd(const int32_t *rowptr, const int32_t *col, int N, int nnz, int H, int C,
-                            int row_begin, int row_end, const float *h, const float *a_src, const float *a_dst,
-                            const float *bias, float neg_slope, int act, float *out, float *out2, float *row_stats,
-                            double p, uint64_t seed, const int64_t *step_counter, int64_t step_value, uint32_t site,
-                            hicgat_stream_t stream);
-int hicgat_gat_agg_drop_bwd_src(const int32_t *rowptr, const int32_t *col, int N, int H, int C, int row_begin,
-                                int row_end, const float *h, const float *a_src, const float *a_dst,
-                                const float *row_stats, int64_t ld_stats, const float *dout, int64_t ld_dout,
-                                const float *att_src, const float *att_dst, float neg_slope, float *dh,
-                                float *da_src, int flags, double p, uint64_t seed, const int64_t *step_counter,
-                                int64_t step_value, uint32_t site, hicgat_stream_t stream);
-int hicgat_gat_attn_mask(const int32_t *rowptr, const int32_t *col, int N, int H, double p, uint64_t seed,
-                         const int64_t *step_counter, int64_t step_value, uint32_t site, uint8_t *mask,
-                         hicgat_stream_t stream);
+ *     hicgat_gat_agg_bwd_rows is unchanged: delta_i = <dout_i, out_i - bias> = sum_k alpha_ik m_ik g_ik
+ *     and da_dst_i = <dout_i, out2_i> - delta_i S3_i are the dropped layer's.
+ *   tiles: the gather writes the remainder's shares of dh and da_src; the tile kernel adds the tiles'
+ *     products (the graph is symmetric, so a row block's tiles are also those of the transposed
+ *     product) and finishes dh (logit terms) and da_src. */
+enum { HICGAT_SRC_ROUND_ROBIN = 1 };
+int hicgat_gat_agg_bwd_src(const hicgat_gat_graph *graph, const hicgat_gat_feats *feats, const float *row_stats,
+                           int64_t ld_stats, const float *dout, int64_t ld_dout, const float *att_src,
+                           const float *att_dst, float *dh, float *da_src, int flags,
+                           const hicgat_attn_drop *drop, const hicgat_gat_tiles *tiles, hicgat_stream_t stream);
+/* mask[e * H + hh] = kept ? 1 : 0 (uint8 [nnz, H], self-looped CSR order) from the device function the
+ * two passes use (tests, tools).  N < 0, a NULL drop or one the passes refuse: HICGAT_EINVAL;
+ * 1 <= H <= 4, else HICGAT_EUNSUPPORTED; N == 0 is a no-op. */
+int hicgat_gat_attn_mask(const int32_t *rowptr, const int32_t *col, int N, int H, const hicgat_attn_drop *drop,
+                         uint8_t *mask, hicgat_stream_t stream);
 
 /* ---- the attention weights as an output, and their backward (gat_attn.hip) ---------------------
  * Reference: PyG 1.7.2 GATConv.forward(x, edge_index, return_attention_weights=True), which
@@ -279,38 +315,6 @@ int hicgat_xagg_param_finish(const float *W, const float *att_src, const float *
                              const float *g_dst, int segs, int64_t seg_stride, int F, int H, int C, float *dW,
                              float *datt_src, float *datt_dst, hicgat_stream_t stream);
 
-/* ---- a4+a5 and the source pass with the dense tiles on the matrix cores (gat_tiles.hip) -------
- * The same results as hicgat_gat_agg_fwd / hicgat_gat_agg_bwd_src (fp32; the tiles' sums are
- * added in another order), with the edge set split in two:
- *   tiles: rows [row_begin, row_end) in blocks of 32 (block b = rows row_begin + 32b ..);
- *     tptr [nrb + 1] (nrb = ceil((row_end - row_begin) / 32)) indexes tcol [ntiles] (a 32-column
- *     block: columns 32*tcol[t] ..) and tmask [ntiles * 32] (bit c of word 32t + i: the edge
- *     (row_begin + 32b + i, 32*tcol[t] + c) exists); tiles of a block in any order, each edge in at
- *     most one tile;
- *   rowptr_s / col_s: the CSR (N + 1 row pointers, rows of the range) of every OTHER edge.
- * rowptr / col (the whole rows) give the softmax statistics.  The tiles' products run as dense
- * 32 x 32 x 32 x 512 blocks on v_mfma_f32_32x32x2_f32 (weights 0 off the edge set).  Built from the
- * CSR by hicgat.graph.build_tiles (a 32x32 tile is dense when it holds >= min_edges edges). */
-int hicgat_gat_agg_fwd_tiled(const int32_t *rowptr, const int32_t *col, const int32_t *rowptr_s,
-                             const int32_t *col_s, const int32_t *tptr, const int32_t *tcol,
-                             const uint32_t *tmask, int ntiles, int N, int H, int C, int row_begin,
-                             int row_end, const float *h, const float *a_src, const float *a_dst,
-                             const float *bias, float neg_slope, int act, float *out, float *out2,
-                             float *row_stats, int splits, void *workspace, size_t workspace_bytes,
-                             hicgat_stream_t stream);
-int hicgat_gat_agg_bwd_src_tiled(const int32_t *rowptr_s, const int32_t *col_s, const int32_t *tptr,
-                                 const int32_t *tcol, const uint32_t *tmask, int ntiles, int N, int H,
-                                 int C, int row_begin, int row_end, const float *h, const float *a_src,
-                                 const float *a_dst, const float *row_stats, int64_t ld_stats,
-                                 const float *dout, int64_t ld_dout, const float *att_src,
-                                 const float *att_dst, float neg_slope, float *dh, float *da_src,
-                                 int splits, void *workspace, size_t workspace_bytes,
-                                 hicgat_stream_t stream);
-/* splits (1..64): the tiles of a row block are spread over `splits` workgroups (a graph with few
- * row blocks, e.g. a dense 2000-node map: 63); splits > 1 needs a 16-B aligned workspace of
- * hicgat_gat_tiled_workspace_bytes(row_end - row_begin, splits) bytes for the partial sums, which
- * one more pass adds in split order. */
-size_t hicgat_gat_tiled_workspace_bytes(int rows, int splits);
 /* Column reductions for the GATConv parameter gradients over N rows (pass pointers offset to a
  * shard's first row for a partial sum; deterministic, two-stage):
  *   datt_src[h,c] = sum_n da_src[n,h] h[n,h,c];  datt_dst likewise with row_stats' da_dst;

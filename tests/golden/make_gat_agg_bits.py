@@ -29,7 +29,7 @@ def main():
     hipcc = subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout
     about = {
         "what": "SHA-256 of the raw little-endian bytes of every output of hicgat.kernels' agg_fwd_act, agg_bwd_rows, "
-                "agg_bwd_dst, agg_bwd_src, agg_drop_fwd and agg_drop_bwd_src on the graph and host-drawn inputs of "
+                "agg_bwd_dst and agg_bwd_src (the first and the last also with drop=DROP) on the graph and host-drawn inputs of "
                 "tests/test_gpu_gat_agg_bits.py (n = 131; DROP = (p, seed, step counter, step_value, site) below), "
                 "output buffers NaN-filled before each call; inputs_sha256: the same of every input",
         "commit": a.commit,

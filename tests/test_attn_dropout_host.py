@@ -114,11 +114,12 @@ def test_train_surface():
 def test_library_exports_the_entry_points():
     from hicgat import _lib
     lib = _lib.load()
-    for s in ("hicgat_gat_agg_drop_fwd", "hicgat_gat_agg_drop_bwd_src", "hicgat_gat_attn_mask"):
+    for s in ("hicgat_gat_agg_fwd", "hicgat_gat_agg_bwd_src", "hicgat_gat_attn_mask"):
         assert hasattr(lib, s) and s in _lib.SIGNATURES, s
-    # the forms they stand beside keep their signatures
-    assert len(_lib.SIGNATURES["hicgat_gat_agg_drop_fwd"][1]) == len(_lib.SIGNATURES["hicgat_gat_agg_fwd"][1]) + 5
-    assert len(_lib.SIGNATURES["hicgat_gat_agg_drop_bwd_src"][1]) == len(_lib.SIGNATURES["hicgat_gat_agg_bwd_src"][1]) + 5
+    # dropout and the dense tiles are operands of those two, not entry points of their own
+    for form in ("drop_fwd", "fwd_tiled", "drop_bwd_src", "bwd_src_tiled"):
+        s = "hicgat_gat_agg_" + form
+        assert not hasattr(lib, s) and s not in _lib.SIGNATURES, s
 
 
 # ---------------------------------------------------------------- the mask's restatement

@@ -297,12 +297,12 @@ def test_row_ranges_at_the_c_abi(H, C):
         out, out2 = (torch.full((N, D), float("nan"), device=DEV) for _ in range(2))
         rs = torch.full((N, 4 * H), float("nan"), device=DEV)
         for r0, r1 in ranges:
-            K.agg_drop_fwd(rp, cl, r0, r1, h, a_src, a_dst, b, 0.2, 0, out, out2, rs, drop)
+            K.agg_fwd_act(rp, cl, r0, r1, h, a_src, a_dst, b, 0.2, 0, out, out2, rs, drop=drop)
         K.agg_bwd_rows(0, N, 0, dout, out, b, out2, None, rs)
         dh = torch.full((N, D), float("nan"), device=DEV)
         da = torch.full((N, H), float("nan"), device=DEV)
         for r0, r1 in ranges:
-            K.agg_drop_bwd_src(rp, cl, r0, r1, h, a_src, a_dst, rs, dout, al, ar, 0.2, dh, da, drop)
+            K.agg_bwd_src(rp, cl, r0, r1, h, a_src, a_dst, rs, dout, al, ar, 0.2, dh, da, drop=drop)
         return out, out2, rs, dh, da
 
     whole = run([(0, N)], (0.5, SEED, None, STEP, SITE))
@@ -457,18 +457,26 @@ def test_c_abi_refusals():
     ctr = torch.zeros(2, dtype=torch.int64, device=DEV)
     odd = ctypes_offset(ctr, 4)
 
+    def graph(r0, r1):
+        return _lib.GatGraph(rowptr=rp.data_ptr(), col=cl.data_ptr(), N=N, nnz=cl.numel(), row_begin=r0, row_end=r1)
+
+    def feats(Hh, Cc):
+        return _lib.GatFeats(h=h.data_ptr(), a_src=a.data_ptr(), a_dst=a.data_ptr(), H=Hh, C=Cc, neg_slope=0.2)
+
+    def drop(p, step, site):
+        return _lib.AttnDrop(p=p, seed=1, step_counter=getattr(step, "value", None), step_value=1, site=site)
+
     def fwd(p=0.5, site=0, Hh=H, Cc=C, r0=0, r1=N, step=None, outp=P(out)):
-        return lib.hicgat_gat_agg_drop_fwd(P(rp), P(cl), N, cl.numel(), Hh, Cc, r0, r1, P(h), P(a), P(a), P(b), 0.2, 0,
-                                           outp, None, P(rs), p, 1, step, 1, site, st)
+        return lib.hicgat_gat_agg_fwd(graph(r0, r1), feats(Hh, Cc), P(b), 0, outp, None, P(rs), drop(p, step, site),
+                                      None, st)
 
     def src(p=0.5, site=0, Hh=H, Cc=C, r0=0, r1=N, step=None, flags=0, ld=4 * H):
-        return lib.hicgat_gat_agg_drop_bwd_src(P(rp), P(cl), N, Hh, Cc, r0, r1, P(h), P(a), P(a), P(rs), ld, P(out), D,
-                                               P(att), P(att), 0.2, P(dh), P(da), flags, p, 1, step, 1,
-                                               site, st)
+        return lib.hicgat_gat_agg_bwd_src(graph(r0, r1), feats(Hh, Cc), P(rs), ld, P(out), D, P(att), P(att), P(dh),
+                                          P(da), flags, drop(p, step, site), None, st)
 
     def mask(p=0.5, site=0, Hh=H, n=N, step=None, m=True):
         buf = torch.zeros((cl.numel(), 4), dtype=torch.uint8, device=DEV)
-        return lib.hicgat_gat_attn_mask(P(rp), P(cl), n, Hh, p, 1, step, 1, site, P(buf) if m else None, st)
+        return lib.hicgat_gat_attn_mask(P(rp), P(cl), n, Hh, drop(p, step, site), P(buf) if m else None, st)
 
     for fn in (fwd, src, mask):
         assert fn() == 0

@@ -89,8 +89,8 @@ def _fp64_gat_train(rowptr, col, h, att_l, att_r, bias, g, mask, ns=0.2, chunk=1
 
 @pytest.mark.parametrize("tiled", [False, True], ids=["gather", "tiled"])
 def test_synth20000_gat_backward_matches_fp64(tiled):
-    """tiled: the dense 32x32 tiles on the matrix cores (hicgat_gat_agg_fwd_tiled /
-    hicgat_gat_agg_bwd_src_tiled, default HICGAT_TILE_MIN), the rest gathered."""
+    """tiled: the dense 32x32 tiles on the matrix cores (hicgat_gat_agg_fwd / hicgat_gat_agg_bwd_src
+    with tiles, default HICGAT_TILE_MIN), the rest gathered."""
     import hicgat
     from hicgat import synth
     K = hicgat.kernels.default()
@@ -113,17 +113,12 @@ def test_synth20000_gat_backward_matches_fp64(tiled):
     tiles = hicgat.graph.build_tiles(adj.rowptr32, adj.col32, 0, n, n, 64) if tiled else None
     if tiled:
         assert tiles.n_dense > 0.4 * adj.device_nnz
-        K.agg_fwd_tiled(adj.rowptr32, adj.col32, tiles, h, a_s, a_d, bias, 0.2, 1, out, out2, rs)
-    else:
-        K.agg_fwd_act(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, bias, 0.2, 1, out, out2, rs)
+    K.agg_fwd_act(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, bias, 0.2, 1, out, out2, rs, tiles=tiles)
     dout = torch.empty(n, 512, device=DEV)
     K.agg_bwd_rows(0, n, 1, g, out, bias, out2, dout, rs)
     dh = torch.empty(n, 512, device=DEV)
     da_src = torch.empty(n, 2, device=DEV)
-    if tiled:
-        K.agg_bwd_src_tiled(tiles, h, a_s, a_d, rs, dout, att_l, att_r, 0.2, dh, da_src)
-    else:
-        K.agg_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, att_l, att_r, 0.2, dh, da_src)
+    K.agg_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, att_l, att_r, 0.2, dh, da_src, tiles=tiles)
     datt_l, datt_r, dbias = K.param_grad(h, dout, da_src, rs, 2)
     # any subset of the three parts (the split the training backward issues: datt_dst + dbias
     # beside the source pass, datt_src behind it) is bitwise the all-parts call

@@ -120,11 +120,11 @@ def outputs(H, C):
     source("src", lambda rs, dout, dh, da, rr: K.agg_bwd_src(rowptr, col, 0, N, h, a_s, a_d, rs, dout, att_l, att_r, NS,
                                                              dh, da, round_robin=rr), dout, rs)
 
-    y, out2, rs_f = forward("drop_fwd", lambda act, out, o2, rs: K.agg_drop_fwd(rowptr, col, 0, N, h, a_s, a_d, bias,
-                                                                               NS, act, out, o2, rs, DROP))
+    y, out2, rs_f = forward("drop_fwd", lambda act, out, o2, rs: K.agg_fwd_act(rowptr, col, 0, N, h, a_s, a_d, bias,
+                                                                              NS, act, out, o2, rs, drop=DROP))
     dout, rs = rows("drop_rows", 1, y, out2, rs_f)
-    source("drop_src", lambda rs, dout, dh, da, rr: K.agg_drop_bwd_src(rowptr, col, 0, N, h, a_s, a_d, rs, dout, att_l,
-                                                                       att_r, NS, dh, da, DROP, round_robin=rr),
+    source("drop_src", lambda rs, dout, dh, da, rr: K.agg_bwd_src(rowptr, col, 0, N, h, a_s, a_d, rs, dout, att_l,
+                                                                  att_r, NS, dh, da, round_robin=rr, drop=DROP),
            dout, rs)
     torch.cuda.synchronize()
     return got

@@ -900,9 +900,10 @@ def test_full_size_synth20000_properties():
     bias = torch.randn(512, device=DEV)
     o = torch.empty(n, 512, device=DEV)
     rs = torch.empty(n, 8, device=DEV)
-    _lib.check(lib.hicgat_gat_agg_fwd(_lib.ptr(adj.rowptr32), _lib.ptr(adj.col32), n, nnz, 2, 256, 0, n,
-                                      _lib.ptr(hconst), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(bias), 0.2, 0,
-                                      _lib.ptr(o), None, _lib.ptr(rs), _lib.stream()), "agg")
+    graph = _lib.GatGraph(rowptr=adj.rowptr32.data_ptr(), col=adj.col32.data_ptr(), N=n, nnz=nnz, row_begin=0, row_end=n)
+    feats = _lib.GatFeats(h=hconst.data_ptr(), a_src=a_s.data_ptr(), a_dst=a_d.data_ptr(), H=2, C=256, neg_slope=0.2)
+    _lib.check(lib.hicgat_gat_agg_fwd(graph, feats, _lib.ptr(bias), 0, _lib.ptr(o), None, _lib.ptr(rs), None, None,
+                                      _lib.stream()), "agg")
     assert torch.allclose(o, 0.75 + bias.expand_as(o), rtol=0, atol=2e-6)
     tr = hicgat.Truth.from_contacts(A, 0.5)
     cc = torch.randn(n, 3, device=DEV).requires_grad_(True)

@@ -61,10 +61,7 @@ def _run(K, adj, n, tiles, seed=1):
     out = torch.empty(n, 512, device=DEV)
     out2 = torch.empty(n, 512, device=DEV)
     rs = torch.empty(n, 8, device=DEV)
-    if tiles is None:
-        K.agg_fwd_act(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, bias, 0.2, 1, out, out2, rs)
-    else:
-        K.agg_fwd_tiled(adj.rowptr32, adj.col32, tiles, h, a_s, a_d, bias, 0.2, 1, out, out2, rs)
+    K.agg_fwd_act(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, bias, 0.2, 1, out, out2, rs, tiles=tiles)
     g = torch.randn(n, 512, device=DEV)
     dout = torch.empty(n, 512, device=DEV)
     K.agg_bwd_rows(0, n, 1, g, out, bias, out2, dout, rs)
@@ -72,8 +69,8 @@ def _run(K, adj, n, tiles, seed=1):
     da_src = torch.empty(n, 2, device=DEV)
     if tiles is None:
         K.agg_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, att_l, att_r, 0.2, dh, da_src)
-    else:
-        K.agg_bwd_src_tiled(tiles, h, a_s, a_d, rs, dout, att_l, att_r, 0.2, dh, da_src)
+    else:   # the tiled source pass reads the remainder's CSR alone
+        K.agg_bwd_src(None, None, None, None, h, a_s, a_d, rs, dout, att_l, att_r, 0.2, dh, da_src, tiles=tiles)
     torch.cuda.synchronize()
     return dict(out=out, out2=out2, rs=rs, dout=dout, dh=dh, da_src=da_src)
 
@@ -139,15 +136,24 @@ def test_tiled_abi_rejects_bad_arguments():
     lib = _lib.lib()
     z = torch.zeros(16, device=DEV)
     p = _lib.ptr(z)
+    a = z.data_ptr()
     s = _lib.stream()
-    fwd = lambda nt, N, H, r0, r1, sp=1, ws=None, wb=0: lib.hicgat_gat_agg_fwd_tiled(  # noqa: E731
-        p, p, p, p, p, p, p, nt, N, H, 256, r0, r1, p, p, p, p, 0.2, 1, p, p, p, sp, ws, wb, s)
+
+    def fwd(nt, N, H, r0, r1, sp=1, ws=None, wb=0):
+        graph = _lib.GatGraph(rowptr=a, col=a, N=N, nnz=0, row_begin=r0, row_end=r1)
+        feats = _lib.GatFeats(h=a, a_src=a, a_dst=a, H=H, C=256, neg_slope=0.2)
+        tiles = _lib.GatTiles(rowptr_s=a, col_s=a, tptr=a, tcol=a, tmask=a, ntiles=nt, splits=sp,
+                              workspace=None if ws is None else a, workspace_bytes=wb)
+        return lib.hicgat_gat_agg_fwd(graph, feats, p, 1, p, p, p, None, tiles, s)
+
     # negative ntiles, row range outside N, unsupported heads
     assert fwd(-1, 4, 2, 0, 4) != 0
     assert fwd(0, 4, 2, 0, 5) != 0
     assert fwd(0, 4, 1, 0, 4) != 0
-    assert lib.hicgat_gat_agg_bwd_src_tiled(p, p, p, None, None, 3, 4, 2, 256, 0, 4, p, p, p, p, 8, p, 512, p, p,
-                                            0.2, p, p, 1, None, 0, s) != 0
+    assert lib.hicgat_gat_agg_bwd_src(
+        _lib.GatGraph(N=4, row_begin=0, row_end=4), _lib.GatFeats(h=a, a_src=a, a_dst=a, H=2, C=256, neg_slope=0.2),
+        p, 8, p, 512, p, p, p, p, 0, None,
+        _lib.GatTiles(rowptr_s=a, col_s=a, tptr=a, tcol=None, tmask=None, ntiles=3, splits=1), s) != 0
     # splits > 1 without (or with too small) a workspace; splits out of range
     need = lib.hicgat_gat_tiled_workspace_bytes(4, 2)
     assert need > 0 and lib.hicgat_gat_tiled_workspace_bytes(4, 1) == 0

@@ -84,7 +84,9 @@ def test_ctypes_signatures_match_header_types():
     typed_pointers = {"hicgat_stream_t *": ctypes.POINTER(_lib.c_p), "hicgat_wgrad_job *": _lib.c_wjobs,
                       "hicgat_colsum_job *": _lib.c_cjobs, "hicgat_gemm_job *": _lib.c_gjobs,
                       "hicgat_tail_weights *": _lib.c_tailw, "hicgat_tail_acts *": _lib.c_taila,
-                      "hicgat_tail_grads *": _lib.c_tailg, "hicgat_tail_gat *": _lib.c_tailgat}
+                      "hicgat_tail_grads *": _lib.c_tailg, "hicgat_tail_gat *": _lib.c_tailgat,
+                      "hicgat_gat_graph *": _lib.c_graph, "hicgat_gat_feats *": _lib.c_feats,
+                      "hicgat_attn_drop *": _lib.c_drop, "hicgat_gat_tiles *": _lib.c_tiles}
     data = {"void", "float", "double", "int32_t", "uint32_t", "int64_t", "uint8_t", "unsigned long long"}
 
     def expected(t, ret=False):

@@ -95,10 +95,10 @@ def main():
         "gat_agg_bwd_src": lambda K: K.agg_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, al, ar,
                                                    0.2, dh, da),
         # attention dropout (p = 0.5, the step by value): the DROP forms of the two gathers
-        "gat_agg_drop_fwd_train": lambda K: K.agg_drop_fwd(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, b, 0.2, 1, out,
-                                                           out2, rs, (0.5, 1, None, 1, 0)),
-        "gat_agg_drop_bwd_src": lambda K: K.agg_drop_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, al,
-                                                             ar, 0.2, dh, da, (0.5, 1, None, 1, 0)),
+        "gat_agg_drop_fwd_train": lambda K: K.agg_fwd_act(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, b, 0.2, 1, out,
+                                                          out2, rs, drop=(0.5, 1, None, 1, 0)),
+        "gat_agg_drop_bwd_src": lambda K: K.agg_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, al,
+                                                        ar, 0.2, dh, da, drop=(0.5, 1, None, 1, 0)),
         "param_grad": lambda K: K.param_grad(h, dout, da, rs, H),
         "pairdist_mse_fused": lambda K: K.fused_loss(coords, truth.buf, n, 0, 0, -1, stats, loss, dc),
         "pairdist_combined": lambda K: K.fused_loss(coords, truth.buf, n, 1, 0, -1, stats, loss, dc),
@@ -107,9 +107,10 @@ def main():
         # the moment-dependent losses' chain (tile, reduce, finalize + combine), beside the combined chains above
         "pairdist_moment": lambda K: K.moment_loss(coords, truth.buf, n, 0, 1.0, stats, loss, dc),
         "pairdist_support_moment": lambda K: K.moment_loss_support(coords, truth.support, n, 0, 1.0, stats, loss, dc),
-        "gat_agg_fwd_tiled": lambda K: K.agg_fwd_tiled(adj.rowptr32, adj.col32, tiles(), h, a_s, a_d, b, 0.2, 1, out,
-                                                       out2, rs),
-        "gat_agg_bwd_src_tiled": lambda K: K.agg_bwd_src_tiled(tiles(), h, a_s, a_d, rs, dout, al, ar, 0.2, dh, da),
+        "gat_agg_fwd_tiled": lambda K: K.agg_fwd_act(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, b, 0.2, 1, out,
+                                                     out2, rs, tiles=tiles()),
+        "gat_agg_bwd_src_tiled": lambda K: K.agg_bwd_src(adj.rowptr32, adj.col32, 0, n, h, a_s, a_d, rs, dout, al, ar,
+                                                         0.2, dh, da, tiles=tiles()),
         "colsum_20000x512": lambda K: K.colsum(out, cs),
         "ln_bwd_256": lambda K: K.ln_act_res_bwd(ya, ya, lns, g256, g256, K.ACT_RELU, 0.0, ya2, g256b, g256c),
         "adam": lambda K: K.adam(flat, g, m, v, flat.numel(), 1e-3, 0.9, 0.999, 1e-8, 1),
